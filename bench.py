@@ -3,17 +3,24 @@
 
     python bench.py --gpus N --steps K --warmup W
                     [--workload deflate-h|deflate|lz77w16|lz77w14|huffman|fse] [--scaling weak|strong] [--bytes B]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 one rank per GPU (RCCL).  A "step" is one pass of the hot path over one batch of synthetic
 enwik-shaped input that is already resident in HBM.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: it makes the seeded input, runs W untimed and K timed steps, writes the
+last step's output if --dump-outputs is given (dump_outputs) and prints the line: value, ms_per_step, sizes and ratio.
+Everything else the line can carry (below, and roofline, cpu_baseline, ratio_vs_ref, the path counters and
+config.input_sha256) is measured only with --full; the kernel times behind `roofline` come from HIP events that --full
+records around every launch of the timed steps.
+
 Default workload = BASELINE.json config 4 as it is worded, "deflate (LZ77 + dynamic Huffman) on enwik9, 32 KiB
 window, 1 MI355X": 10^9 enwik-shaped bytes cut into 15 259 independent 64 KiB blocks; per block the reference
 tokeniser (algorithms/deflate/lz77.c:199-280, fresh table per block, token sequence byte-exact) followed by the
-per-block dynamic Huffman stage the reference leaves as a TODO (lz77.c:279; "mode H", include/mi_codec.h).  The same
-line also carries
+per-block dynamic Huffman stage the reference leaves as a TODO (lz77.c:279; "mode H", include/mi_codec.h).  With --full
+the same line also carries
     mode_T        the token-only mode (the reference's own byte-token stream) timed the same way,
     shard_125MB   config 5's per-GPU shape (1/8 of enwik9 = 1 908 blocks) on this one GPU,
     ratio_vs_ref  own output size against the reference's shipped compress() output (persistent table,
@@ -30,8 +37,8 @@ The north star's RCCL gather of the compressed streams to rank 0 (sharded.gather
 group of point-to-point transfers over xGMI) is INSIDE the timed region for --scaling strong (config 5 as worded: one
 enwik9, 65 MB of mode-H stream per peer) and OUTSIDE it for the default weak scaling, where every rank owns a whole
 enwik9-sized shard and the path itself has no data-path collective (each rank's stream is a finished product; gathering
-8 x 0.5 GB into one GPU is not part of any BASELINE config): there it is run and timed once after the timed region and
-reported as `gather`.  --gather / --no-gather force it in or out.
+8 x 0.5 GB into one GPU is not part of any BASELINE config): there --full runs and times it once after the timed region
+and reports it as `gather`.  --gather / --no-gather force it in or out.
 """
 import argparse
 import json
@@ -61,9 +68,14 @@ def parse_args():
     ap.add_argument("--gather", dest="gather", action="store_true", default=None,
                     help="N>1: gather the compressed streams to rank 0 inside the timed region (default for --scaling strong)")
     ap.add_argument("--no-gather", dest="gather", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: kernel times and roofline, round trip and decode_gbps, "
+                         "path counters, input digest, gather outside the timed region, CPU baseline, ratio_vs_ref and the one-GPU extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32/float64, rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="target duration of each leg of the headline's CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip mode_T / shard_125MB / end_to_end (A/B runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and ratio_vs_ref")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip mode_T / shard_125MB / end_to_end (A/B runs)")
     ap.add_argument("--multi-devices", default=None,
                     help="e.g. 0,1,2,3: ONE process, the C boundary's mi_lz_encode_multi_dev over these devices (config 5 through "
                          "csrc/multi.hip: contiguous block ranges, RCCL gather into the first device; a device may repeat). "
@@ -71,7 +83,10 @@ def parse_args():
     ap.add_argument("--seed", type=int, default=12345)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearsal of the N>1 path on a box with fewer GPUs than ranks (ranks share devices)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 DESC = {
@@ -150,6 +165,43 @@ def timed_steps(codec, x, steps, warmup, sync, after_step=None):
         step()
     sync()
     return time.perf_counter() - t0, holder["h"]
+
+
+DUMP_SAMPLE = 1 << 23       # stream bytes --dump-outputs writes at most: 32 MB as float32, under the 64 MB cap with the tables
+
+
+def dump_outputs(out_dir, h, seed):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as DIR/<name>.npy in float32 or
+    float64 (every value exact).  `stream_sample` = the compressed stream's bytes at DUMP_SAMPLE sorted positions drawn
+    from [0, nbytes) by a torch.Generator seeded with --seed (the whole stream when it is not longer): the same arguments
+    give the same positions, so two builds compare output for output.  Beside it the stream's table whole —
+    `block_table_bits` (per-block bit offsets of the LZ / mode-H / FSE streams) or `total_bits` — and, for whole-buffer
+    Huffman, the code table (`codes`, `lengths`)."""
+    import numpy as np
+    arrays = {}
+    if hasattr(h, "words"):                               # whole-buffer Huffman: uint32 words, bits from the low end
+        nb = (h.total_bits + 7) // 8
+        stream = h.words.view(torch.uint8)[:nb]
+        arrays["codes"] = h.codes.astype(np.float64)
+        arrays["lengths"] = h.lengths.astype(np.float32)
+        arrays["total_bits"] = np.array([h.total_bits], np.float64)
+    else:
+        nb = h.nbytes
+        stream = h.data[:nb]
+        table = h.block_bits if hasattr(h, "block_bits") else getattr(h, "offsets", None)
+        if table is not None:
+            arrays["block_table_bits"] = table.cpu().numpy().astype(np.float64)
+        else:
+            arrays["total_bits"] = np.array([h.total_bits], np.float64)
+    if nb > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(seed)
+        pos = torch.randint(0, nb, (DUMP_SAMPLE,), generator=g).sort().values.to(stream.device)
+        stream = stream[pos]
+    arrays["stream_sample"] = stream.float().cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_encode(workload, sample):
@@ -478,15 +530,21 @@ def main_multi_devices(args):
         h = mm.compress_dev(shards, n, p, mode_h=mode_h)           # returns synchronised (the gather included)
     dt = time.perf_counter() - t0
     torch.cuda.set_device(devs[0])
-    back = lz.decompress_h(h) if mode_h else lz.decompress(h)
-    ok = bool(torch.equal(back, whole))
-    print(json.dumps({"metric": "encode GB/s on enwik9 at 1/2/4/8 MI355X; ratio vs ref; round-trip bit-exact", "value": round(n * args.steps / dt / 1e9, 3),
-                      "unit": "GB/s", "n_gpus": len(set(devs)), "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-                      "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-                      "config": {"workload": f"{DESC[args.workload]}; {n} enwik-shaped bytes, ONE process over devices {devs} "
-                                             f"(mi_lz_encode_multi_dev, transport {mm.transport}), gather to device {devs[0]} inside the timed region",
-                                 "input_sha256": synth.digest(whole), "compressed_bytes_job": int(h.nbytes), "ratio": round(n / max(h.nbytes, 1), 4)},
-                      "roundtrip": ok}), flush=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, args.seed)
+    line = {"metric": "encode GB/s on enwik9 at 1/2/4/8 MI355X; ratio vs ref; round-trip bit-exact", "value": round(n * args.steps / dt / 1e9, 3),
+            "unit": "GB/s", "n_gpus": len(set(devs)), "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "config": {"workload": f"{DESC[args.workload]}; {n} enwik-shaped bytes, ONE process over devices {devs} "
+                                   f"(mi_lz_encode_multi_dev, transport {mm.transport}), gather to device {devs[0]} inside the timed region",
+                       "compressed_bytes_job": int(h.nbytes), "ratio": round(n / max(h.nbytes, 1), 4)}}
+    ok = True
+    if args.full:
+        back = lz.decompress_h(h) if mode_h else lz.decompress(h)
+        ok = bool(torch.equal(back, whole))
+        line["config"]["input_sha256"] = synth.digest(whole)
+        line["roundtrip"] = ok
+    print(json.dumps(line), flush=True)
     mm.close()
     if not ok:
         sys.exit(3)
@@ -502,7 +560,7 @@ def main():
     dist = None
     # the all-cores CPU baseline needs worker processes: fork them NOW, before anything touches the GPU
     pool = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             pool = CpuPool()
         except Exception:
@@ -541,7 +599,7 @@ def main():
     n = x.numel()
     torch.cuda.synchronize()
     # digest of the rank-0 buffer: the generator is byte-reproducible (synth.py), so this field is too
-    input_digest = synth.digest(x) if rank == 0 else None
+    input_digest = synth.digest(x) if rank == 0 and args.full else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -564,25 +622,30 @@ def main():
             after(h)
         h = None
     barrier()
-    ctx.set_profiling(True)
-    ctx.kernel_times()              # reset
+    if args.full:
+        ctx.set_profiling(True)
+        ctx.kernel_times()          # reset
     dt, last = timed_steps(codec, x, args.steps, 0, barrier, after)
-    ctx.set_profiling(False)
-    ktimes = ctx.kernel_times()
+    if args.full:
+        ctx.set_profiling(False)
+        ktimes = ctx.kernel_times()
     c = codec.nbytes(last)
-    # what the timed steps met (mi_lz_path_stats / mi_order_violations): blocks on the fallback pipeline, parts above 2 560
-    # entries, sorts found out of order — all 0 on text; a corpus that lives in the fallback would otherwise only be a slow number
-    path = ctx.path_stats()
-    path["order_violations"] = ctx.order_violations()
+    if args.full:
+        # what the timed steps met (mi_lz_path_stats / mi_order_violations): blocks on the fallback pipeline, parts above 2 560
+        # entries, sorts found out of order — all 0 on text; a corpus that lives in the fallback would otherwise only be a slow number
+        path = ctx.path_stats()
+        path["order_violations"] = ctx.order_violations()
 
     t = torch.tensor([dt], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, args.seed)
 
     # ---- outside the timed region (weak scaling): the RCCL gather of the streams to rank 0, timed on its own
     gather_report = None
-    if can_gather and not gather and args.gather is None:
+    if args.full and can_gather and not gather and args.gather is None:
         try:
             gather_streams(last)                      # warm-up: communicators, receive buffers
             barrier()
@@ -597,19 +660,21 @@ def main():
         except Exception as e:                        # reported, never fatal for the throughput line
             gather_report = {"ms": None, "error": repr(e)[:200]}
     # ---- outside the timed region: round trip of the last output on every rank
-    back = codec.decode(last)
-    rt_ok = bool(torch.equal(back, x))
-    del back
-    torch.cuda.synchronize()
-    td0 = time.perf_counter()
-    back = codec.decode(last)                         # the decoders synchronise their stream themselves (status word)
-    torch.cuda.synchronize()
-    decode_gbps = round(n / (time.perf_counter() - td0) / 1e9, 2)
-    del back
-    if dist is not None:
-        f = torch.tensor([1 if rt_ok else 0], dtype=torch.int32, device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(f, op=dist.ReduceOp.MIN)
-        rt_ok = bool(int(f.item()))
+    rt_ok = True
+    if args.full:
+        back = codec.decode(last)
+        rt_ok = bool(torch.equal(back, x))
+        del back
+        torch.cuda.synchronize()
+        td0 = time.perf_counter()
+        back = codec.decode(last)                     # the decoders synchronise their stream themselves (status word)
+        torch.cuda.synchronize()
+        decode_gbps = round(n / (time.perf_counter() - td0) / 1e9, 2)
+        del back
+        if dist is not None:
+            f = torch.tensor([1 if rt_ok else 0], dtype=torch.int32, device=dev if args.backend == "nccl" else "cpu")
+            dist.all_reduce(f, op=dist.ReduceOp.MIN)
+            rt_ok = bool(int(f.item()))
     csum = torch.tensor([c], dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
     if dist is not None:
         dist.all_reduce(csum, op=dist.ReduceOp.SUM)
@@ -617,10 +682,9 @@ def main():
 
     if rank == 0:
         value = n_job * args.steps / dt / 1e9
-        roof = roofline_of(args.workload, n, c, ktimes, args.steps, dt)
 
         extras = {}
-        single = world == 1 and not args.no_extras
+        single = args.full and world == 1 and not args.no_extras
         cpu_on = not args.no_cpu_baseline
         if single and args.workload == "deflate-h":
             # the token-only mode, timed the same way (what BENCH_r01 carried as its headline; a launch is credited
@@ -790,7 +854,7 @@ def main():
 
         cpu = None
         ratio_vs_ref = None
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is a rank-0, N = 1 measurement
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is a rank-0, N = 1 measurement
             cpu, sample = cpu_baseline(args.workload, x, pool, seconds=args.cpu_seconds)
             # ratio vs the reference's own output on (a prefix of) the same sample
             nr = min(len(sample), 64 * 1024 * 1024)
@@ -813,16 +877,19 @@ def main():
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
             "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": f"{DESC[args.workload]}; {n_job} enwik-shaped bytes in the job, {n} on rank 0",
-                       "input_sha256": input_digest, "input_seed": args.seed,
+                       "input_seed": args.seed,
                        "mode": {"deflate-h": "H", "deflate": "T"}.get(args.workload),
                        "input_bytes_job": n_job, "input_bytes_rank0": n, "compressed_bytes_job": c_job, "compressed_bytes_rank0": int(c),
                        "ratio": round(n_job / max(c_job, 1), 4), "gather_to_rank0": bool(gather),
                        "parallelism": f"blocks sharded over {world} GPU(s), {args.scaling} scaling"},
-            "ratio": round(n_job / max(c_job, 1), 4), "ratio_vs_ref": ratio_vs_ref, "roundtrip": rt_ok, "decode_gbps": decode_gbps, "gather": gather_report,
-            "roofline": roof, "cpu_baseline": cpu,
-            "fallback_blocks": path["fallback_blocks"], "wide_parts": path["wide_parts"], "order_violations": path["order_violations"],
+            "ratio": round(n_job / max(c_job, 1), 4),
         }
-        line.update(extras)
+        if args.full:
+            line["config"]["input_sha256"] = input_digest
+            line.update({"ratio_vs_ref": ratio_vs_ref, "roundtrip": rt_ok, "decode_gbps": decode_gbps, "gather": gather_report,
+                         "roofline": roofline_of(args.workload, n, c, ktimes, args.steps, dt), "cpu_baseline": cpu,
+                         "fallback_blocks": path["fallback_blocks"], "wide_parts": path["wide_parts"], "order_violations": path["order_violations"]})
+            line.update(extras)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

@@ -27,7 +27,7 @@ for rep in $(seq 1 "$REPS"); do
     J="$OUT/${TAG}_${name}_$rep.json"
     # (env before python: nothing has touched the GPU yet in this shell)
     env "${ENVS[@]}" timeout -k 10 600 python bench.py --workload "$WL" --bytes "$BYTES" --steps "$STEPS" --warmup "$WARM" \
-        --no-cpu-baseline --no-extras > "$J" 2> "${J%.json}.err" || { echo "$name failed"; tail -5 "${J%.json}.err"; exit 1; }
+        --full --no-cpu-baseline --no-extras > "$J" 2> "${J%.json}.err" || { echo "$name failed"; tail -5 "${J%.json}.err"; exit 1; }
     python - "$J" "$name" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ TAG=${1:-r02}; shift || true
 OUT=gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-extras --bytes 268435456 $*"
+ARGS="--steps 2 --warmup 1 --full --no-cpu-baseline --no-extras --bytes 268435456 $*"
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_BUSY_CU_CYCLES" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" \
