@@ -90,7 +90,7 @@ mi_status mi_ctx_create(mi_ctx **out, int device)
         bool ok = (sp_ && sp_[0] == 'l') ? hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, lo) == hipSuccess
                                          : hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess;
         ok = ok && hipStreamCreateWithPriority(&c->fb, hipStreamNonBlocking, lo) == hipSuccess;
-        // stage C at raised priority: k_lz_parse_emit wants a whole CU's LDS and only gets one when all three workgroups of
+        // stage C at raised priority: k_lz_parse_emit wants a whole CU's LDS and only gets one when all the workgroups of
         // k_lz2_find on it have left — first in line it spans 4.5 ms per launch instead of 6.4 and the step is 0.6 % shorter
         // (MI_PARSE_PRIO=0: default priority, for A/B)
         const char *pp = getenv("MI_PARSE_PRIO");

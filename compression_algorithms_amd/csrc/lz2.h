@@ -12,9 +12,10 @@
 #define LZ2_CAP       4096u                 // largest part stage 2 takes (entries): k_lz2_find_wide, 76 KiB of LDS, two workgroups per CU
 #endif
 #ifndef LZ2_CAP_S
-#define LZ2_CAP_S     2560u                 // what the partition aims for: k_lz2_find, 51 KiB, THREE workgroups per CU (same-box A/B against
-                                            // parts of 4096 everywhere: 19.7 -> 20.4 GB/s).  A part between the two exists only where no
-                                            // certified cut lies within 2560 entries (one cluster of 2561..4096 entries: runs of one byte).
+#define LZ2_CAP_S     2048u                 // what the partition aims for: k_lz2_find, < 40 KiB, FOUR workgroups per CU (2560 entries and
+                                            // three per CU: DESIGN.md 4.4; parts of 4096 everywhere, two per CU: 19.7 -> 20.4 GB/s).  A part
+                                            // between the two exists only where no certified cut lies within 2048 entries (one cluster of
+                                            // 2049..4096 entries: runs of one byte).  The counters of k_lz2_find are 16-bit up to 2048 only.
 #endif
 #ifndef LZ2_THREADS
 #define LZ2_THREADS   512                   // k_lz2_find workgroup
@@ -32,8 +33,9 @@ static_assert(LZ2_CAP % LZ2_THREADS == 0 && LZ2_CAP_S % LZ2_THREADS == 0 && LZ2_
 // for larger tables).  Round 3 had 32 part numbers for ~27 parts of text and a silent exit to the fallback pipeline (a tenth
 // of the speed) at the 33rd; an A/B build with parts of 2048 entries took that exit on every block.
 static_assert(2u * (LZ_MAX_BLOCK / LZ2_CAP_S + 1u + 16u) + 2u <= LZ2_MAXPARTS, "a block could need more parts than the partition can number");
-#define LZ2_GRID_PARTS 32u                  // k_lz2_find's grid covers this many parts per block (text: 26-27); parts listed beyond
-                                            // the grid (never seen on text) are taken by the looping k_lz2_find_wide
+#define LZ2_GRID_PARTS 40u                  // k_lz2_find's grid covers this many parts per block (text: ~33 at 2048 entries); parts listed
+                                            // beyond the grid (never seen on text) are taken by the looping k_lz2_find_wide
+static_assert(LZ2_GRID_PARTS * LZ2_CAP_S >= 5u * LZ_MAX_BLOCK / 4u, "the grid must cover a full block of text with room to spare");
 #ifndef LZ2_BIG
 #define LZ2_BIG       8u                    // clusters of at least this many entries leave k_lz2_find (8 or 16: the register replay holds < 16)
 #endif

@@ -1,7 +1,7 @@
 // lz2_find.hip — stage 2 and 3 of the LDS-resident match finder.
 //
-//   k_lz2_find        one workgroup per part (<= LZ2_CAP_S = 2560 positions whose clusters lie inside the part, certified by
-//                     stage 1; 51 KiB of LDS, three per CU.  k_lz2_find_wide: the same body for the rare parts of up to
+//   k_lz2_find        one workgroup per part (<= LZ2_CAP_S = 2048 positions whose clusters lie inside the part, certified by
+//                     stage 1; < 40 KiB of LDS, four per CU.  k_lz2_find_wide: the same body for the rare parts of up to
 //                     LZ2_CAP = 4096).  Everything happens in LDS: mixed words (home = mask, equality = equality), positions
 //                     sorted by home (2-3 stable 8-bit radix passes), clusters / dense home slots / word ids / "mixed"
 //                     bits from the parking sweep, (cluster, time) order by cursor placement.  Then
@@ -133,21 +133,25 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     uint16_t *const s_g = s_gr;                          // cluster number by j; later occ
     uint16_t *const s_r = s_gr + CAP;                // dense home slot by j; later cand by replay index
     __shared__ uint16_t s_pid[CAP + 2];             // word id by j (position of the first occurrence); then s_gstart; last cand by j
-    __shared__ uint32_t s_cnt[LZ2_NWAVES + 1][256];   // radix counters, [digit][wave + pad] (lz_common.h)
+    // radix counters, [digit][wave + pad] (lz_common.h): a count is at most CAP, so 16 bits hold it — 4.5 KiB instead of 9,
+    // part of the budget of four workgroups per CU; the wide instance keeps 32 bits, because the cluster cursors and the
+    // export lists that live in the counters after the sorts need 8 KiB there (static_asserts below)
+    using Cnt = typename std::conditional<(CAP <= 2048u), uint16_t, uint32_t>::type;
+    __shared__ __attribute__((aligned(16))) Cnt s_cnt[LZ2_NWAVES + 1][256];
     __shared__ uint32_t s_bm[CAP / 32 + 2];
     __shared__ uint32_t s_mix[CAP / 32 + 2];        // bit g: cluster g holds more than one home or more than one word ("mixed")
     __shared__ int32_t  s_i32[18];
     __shared__ uint32_t s_zslot, s_zgid, s_nbigl, s_ngroups;
-    // LDS diet: two of these workgroups share a CU, and whatever they leave (160 KiB - 2 x this kernel) is all that the
-    // replay kernels of the previous batch can use beside them.  Arrays that are dead by then are reused:
+    // LDS diet: four of these workgroups share a CU (two of the wide instance), and whatever they leave is all that the replay
+    // kernels of the previous batch can use beside them.  Arrays that are dead by then are reused:
     //   s_gstart (replay index of the head of every cluster) lives in s_pid, dead between the permutation and the final
     //            reordering of the results;
     //   s_big    ({s, e, global dst} of the clusters this part exports) and s_quiet (quiet clusters of >= LZ2_BIG
     //            entries) live in the radix counters, dead after the second sort.
     uint16_t *const s_gstart = s_pid;
-    uint32_t *const s_big = &s_cnt[0][0];
-    uint16_t *const s_quiet = reinterpret_cast<uint16_t *>(&s_cnt[0][0] + 3 * (CAP / LZ2_BIG));
-    static_assert(3 * (CAP / LZ2_BIG) * 4 + 2 * (CAP / LZ2_BIG) * 2 <= sizeof(uint32_t) * LZ2_NWAVES * 256, "export lists must fit the radix counters");
+    uint32_t *const s_big = reinterpret_cast<uint32_t *>(&s_cnt[0][0]);
+    uint16_t *const s_quiet = reinterpret_cast<uint16_t *>(s_big + 3 * (CAP / LZ2_BIG));
+    static_assert(3 * (CAP / LZ2_BIG) * 4 + 2 * (CAP / LZ2_BIG) * 2 <= sizeof(s_cnt), "export lists must fit the radix counters");
 
     const int tid = threadIdx.x;
     const uint32_t lb = (uint32_t)item & 0xFFFFu, part = (uint32_t)(item >> 16) & 0xFFu;
@@ -155,12 +159,16 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     long long tk = clock64();
     // stop_phase exists only in a measurement build (make EXTRA=-DMI_MEASURE, scripts/phase_pmc.sh): the shipped library never
     // leaves early, whatever the environment says (a stray MI_LZ_STOP_PHASE produced wrong streams with MI_OK)
+// The phase counters (MI_LZ_DEBUG=1) are compiled into measurement builds only, too: the clock and the counter pointer held
+// SGPRs across the whole body, and the shipped kernel has to stay within 80 of them (four workgroups per CU, k_lz2_find).
 #ifdef MI_MEASURE
 #define LZ2_STOP(k) if ((k) < 7 && sc.stop_phase == (uint32_t)(k) + 1u) return
+#define LZ2_DBG     sc.dbg
 #else
 #define LZ2_STOP(k) do { } while (0)
+#define LZ2_DBG     ((uint64_t *)nullptr)
 #endif
-#define LZ2_TICK(k) do { if (sc.dbg && tid == 0) { long long t2 = clock64(); atomicAdd((unsigned long long *)&sc.dbg[k], (unsigned long long)(t2 - tk)); tk = t2; } \
+#define LZ2_TICK(k) do { if (LZ2_DBG && tid == 0) { long long t2 = clock64(); atomicAdd((unsigned long long *)&LZ2_DBG[k], (unsigned long long)(t2 - tk)); tk = t2; } \
                          LZ2_STOP(k); } while (0)
     // (only parts of blocks that did not fall back are listed; the list position and length ride in the item, so the list
     //  loads below do not wait for the block's meta record)
@@ -179,9 +187,12 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     const uint32_t plo_ = mt->part_lo[part];
     const uint32_t phi_ = (part + 1 < mt->nparts) ? mt->part_lo[part + 1] : T;
     const bool three = (phi_ - plo_) > 65536u;
-    uint32_t *const cntA = &s_cnt[0][0];
-    uint32_t (*const s_cntB)[256] = reinterpret_cast<uint32_t (*)[256]>(s_gr);       // 9 KiB of the 16 (s_g / s_r are idle until the sweep)
-    uint32_t *const cntB = &s_cntB[0][0];
+    Cnt *const cntA = &s_cnt[0][0];
+    Cnt (*const s_cntB)[256] = reinterpret_cast<Cnt (*)[256]>(s_gr);                 // (s_g / s_r are idle until the sweep)
+    Cnt *const cntB = &s_cntB[0][0];
+    // the second pass's counters must fit s_gr: with 32-bit counters and parts of 2048 entries they did not (9 KiB on 8), and
+    // the zeroing and counting ran 1 KiB into whatever LDS array follows — the round-3 A/B build with parts of 2048 entries
+    static_assert(sizeof(s_cnt) <= sizeof(s_gr), "the second pass's radix counters must fit s_g | s_r");
     constexpr uint32_t RST = LZ2_NWAVES + 1;                                        // counter stride of radix_pass
     const uint32_t seg = radix_seg<LZ2_NWAVES>(m), seg_inv = (uint32_t)((0x100000000ull + seg - 1u) / seg);   // i / seg = umulhi(i, seg_inv) for i < 2^16
     for (uint32_t i = tid; i < 256u * RST; i += LZ2_THREADS) { cntA[i] = 0; cntB[i] = 0; }
@@ -271,7 +282,7 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
                 // value identifies the word: keep it instead of the word — the home is a mask away, equality is equality
                 const uint32_t mx = lz_mix32(w);
                 s_word[j] = mx;
-                atomicAdd(&cntA[(((((mx & Tmask) - base) & Tmask) - plo_) & 255u) * RST + __umulhi(j, seg_inv)], 1u);
+                radix_cnt_add(cntA, (((((mx & Tmask) - base) & Tmask) - plo_) & 255u) * RST + __umulhi(j, seg_inv), 1u);
             }
         }
     }
@@ -289,19 +300,19 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     if (three) {
         radix_pass<LZ2_NWAVES, 8, uint32_t>(m, s_cnt, [&](uint32_t i) { return i; },
             [&](uint32_t e) { return keyp(e) & 255u; }, [&](uint32_t d, uint32_t e) { s_j0[d] = (uint16_t)e; }, arank, nullptr, true,
-            [&](uint32_t d, uint32_t e) { atomicAdd(&cntB[((keyp(e) >> 8) & 255u) * RST + __umulhi(d, seg_inv)], 1u); });
+            [&](uint32_t d, uint32_t e) { radix_cnt_add(cntB, ((keyp(e) >> 8) & 255u) * RST + __umulhi(d, seg_inv), 1u); });
         for (uint32_t i = tid; i < 256u * RST; i += LZ2_THREADS) cntA[i] = 0;         // (the next pass opens with a barrier)
         radix_pass<LZ2_NWAVES, 8, uint32_t>(m, s_cntB, [&](uint32_t i) { return (uint32_t)s_j0[i]; },
             [&](uint32_t e) { return (keyp(e) >> 8) & 255u; }, [&](uint32_t d, uint32_t e) { s_j1[d] = (uint16_t)e; }, arank, nullptr, true,
-            [&](uint32_t d, uint32_t e) { atomicAdd(&cntA[((keyp(e) >> 16) & 255u) * RST + __umulhi(d, seg_inv)], 1u); });
+            [&](uint32_t d, uint32_t e) { radix_cnt_add(cntA, ((keyp(e) >> 16) & 255u) * RST + __umulhi(d, seg_inv), 1u); });
         radix_pass<LZ2_NWAVES, 8, uint32_t>(m, s_cnt, [&](uint32_t i) { return (uint32_t)s_j1[i]; },
             [&](uint32_t e) { return (keyp(e) >> 16) & 255u; }, [&](uint32_t d, uint32_t e) { s_j0[d] = (uint16_t)e; }, arank, nullptr, true);
     } else {
         radix_pass<LZ2_NWAVES, 8, uint32_t>(m, s_cnt, [&](uint32_t i) { return i; },
-            [&](uint32_t e) { return keyp(e) & 255u; }, [&](uint32_t d, uint32_t e) { s_j1[d] = (uint16_t)e; }, arank, sc.dbg, true,
-            [&](uint32_t d, uint32_t e) { atomicAdd(&cntB[((keyp(e) >> 8) & 255u) * RST + __umulhi(d, seg_inv)], 1u); });
+            [&](uint32_t e) { return keyp(e) & 255u; }, [&](uint32_t d, uint32_t e) { s_j1[d] = (uint16_t)e; }, arank, LZ2_DBG, true,
+            [&](uint32_t d, uint32_t e) { radix_cnt_add(cntB, ((keyp(e) >> 8) & 255u) * RST + __umulhi(d, seg_inv), 1u); });
         radix_pass<LZ2_NWAVES, 8, uint32_t>(m, s_cntB, [&](uint32_t i) { return (uint32_t)s_j1[i]; },
-            [&](uint32_t e) { return (keyp(e) >> 8) & 255u; }, [&](uint32_t d, uint32_t e) { s_j0[d] = (uint16_t)e; }, arank, sc.dbg, true);
+            [&](uint32_t e) { return (keyp(e) >> 8) & 255u; }, [&](uint32_t d, uint32_t e) { s_j0[d] = (uint16_t)e; }, arank, LZ2_DBG, true);
     }
     (void)srt;
 
@@ -445,7 +456,7 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     //      (cluster numbers are < CAP <= 4096: two 6-bit passes, fewer ballots and a shorter offset scan than 8 + 8)
     static_assert(CAP <= 8192, "cluster numbers must fit 13 bits");
     constexpr int GB2 = CAP > 4096 ? 7 : 6;          // bits of the second cluster-number pass
-    static_assert(2 * CAP <= sizeof(uint32_t) * (LZ2_NWAVES + 1) * 256, "the cluster cursors live in the radix counters");
+    static_assert(2 * CAP <= sizeof(s_cnt), "the cluster cursors live in the radix counters");
     if (arank & LZP_ARANK) {
         // ONE pass, no counting: the sweep left every cluster's first replay index as a 16-bit cursor; an entry's place is its
         // cluster's cursor, post-incremented — in TIME order.  Time order needs every cursor to be advanced by one wave only
@@ -455,7 +466,7 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
         // Replaces two 6-bit radix passes (count, scan, scatter each): 20 k -> ~8 k cycles per part.
         // Only clusters with MORE THAN ONE HOME need it (a cluster of one home is in time order already: the home sort is stable);
         // their entries are compacted first, time order kept, so the eight waves walk a short list instead of the whole part.
-        uint32_t *cur32 = &s_cnt[0][0];
+        uint32_t *cur32 = reinterpret_cast<uint32_t *>(&s_cnt[0][0]);
         const uint32_t wv = (uint32_t)tid >> 6, ln = (uint32_t)tid & 63u;
         auto multi = [&](uint32_t g) -> bool { return (s_bm[g >> 5] >> (g & 31u)) & 1u; };
         for (uint32_t k = k0; k < k1; ++k) { const uint32_t j = s_j0[k]; if (!multi(s_g[j])) s_j1[k] = (uint16_t)j; }
@@ -611,9 +622,9 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
             }
         const uint32_t ncl = s_ncl;
         LZ2_TICK(13);
-        if (sc.dbg && tid == 0) { atomicAdd((unsigned long long *)&sc.dbg[23], (unsigned long long)ncl); atomicAdd((unsigned long long *)&sc.dbg[24], (unsigned long long)nbig);
-                                  atomicAdd((unsigned long long *)&sc.dbg[25], (unsigned long long)s_ent); atomicAdd((unsigned long long *)&sc.dbg[26], (unsigned long long)s_nquiet);
-                                  atomicAdd((unsigned long long *)&sc.dbg[27], (unsigned long long)m); atomicAdd((unsigned long long *)&sc.dbg[28], (unsigned long long)s_ngroups); }
+        if (LZ2_DBG && tid == 0) { atomicAdd((unsigned long long *)&LZ2_DBG[23], (unsigned long long)ncl); atomicAdd((unsigned long long *)&LZ2_DBG[24], (unsigned long long)nbig);
+                                  atomicAdd((unsigned long long *)&LZ2_DBG[25], (unsigned long long)s_ent); atomicAdd((unsigned long long *)&LZ2_DBG[26], (unsigned long long)s_nquiet);
+                                  atomicAdd((unsigned long long *)&LZ2_DBG[27], (unsigned long long)m); atomicAdd((unsigned long long *)&LZ2_DBG[28], (unsigned long long)s_ngroups); }
         // ---- clusters of ONE word (one home, every entry the same word: most clusters of a text) have a closed form.  find()
         //      for that word only ever looks at the home slot: it holds the "anchor", the copy that was inserted when the slot
         //      was free — the first entry, then, once the anchor has been retired (lz77.c:70-76: its position + W < p), the
@@ -691,7 +702,7 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     uint16_t *cout = sc.cand + (size_t)lb * LZ_MAX_BLOCK + pstart;
     for (uint32_t j = tid; j < m; j += LZ2_THREADS) cout[j] = cand_j[j];
     LZ2_TICK(6);
-    if (sc.dbg && tid == 0) atomicAdd((unsigned long long *)&sc.dbg[15], 1ull);
+    if (LZ2_DBG && tid == 0) atomicAdd((unsigned long long *)&LZ2_DBG[15], 1ull);
 }
 
 
@@ -701,9 +712,11 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
 // the whole body: 84 -> 176 VGPRs, one workgroup per CU instead of two (forced back to 128 VGPRs it spills) — and the
 // hardware dispatcher already IS a dynamic scheduler: ~13 k empty workgroups per batch cost nothing measurable.
 // XCD-aware order: workgroup ids go round the 8 XCDs (each with its own L2), the work list holds a block's parts one
-// after the other — so give every XCD a CONTIGUOUS eighth of the list: the ~26 parts of a block then gather their
+// after the other — so give every XCD a CONTIGUOUS eighth of the list: the ~33 parts of a block then gather their
 // words from one L2 instead of pulling the block's 64 KiB into all eight (HBM fetch of this kernel: profiles/).
-__global__ __launch_bounds__(LZ2_THREADS)
+// __launch_bounds__(512, 8): eight waves per SIMD = four workgroups per CU, together with the LDS of lz2_find_part<2048>
+// (< 40 KiB): registers above 64 VGPRs / 80 SGPRs would cap the occupancy below that (tests/test_find_budget.py)
+__global__ __launch_bounds__(LZ2_THREADS, 8)
 void k_lz2_find(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
 {
     // the grid is a multiple of 8 (lz2_stage_find) and takes the first gridDim.x listed parts; what a batch lists beyond it
@@ -1197,10 +1210,10 @@ mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, ui
     return MI_OK;
 }
 
-// stage A2: per-part find (LDS heavy: three workgroups per CU)
+// stage A2: per-part find (LDS heavy: four workgroups per CU)
 static uint32_t lz2_find_grid(const LzP &P, uint32_t nb)
 {
-    // the partition lists a block's parts (greedy, data dependent: 26-27 for a full block of text); the grid covers
+    // the partition lists a block's parts (greedy, data dependent: ~33 for a full block of text); the grid covers
     // LZ2_GRID_PARTS per block, rounded up to the 8 XCD slices of the kernel's workgroup mapping (a grid that is not a multiple
     // of 8 would leave items of the last row unassigned: ADVICE r3), the looping wide kernel takes whatever lies beyond
     const uint32_t parts = P.block / 64u + 1u < LZ2_GRID_PARTS ? P.block / 64u + 1u : LZ2_GRID_PARTS;
@@ -1216,7 +1229,7 @@ mi_status lz2_stage_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_
     return MI_OK;
 }
 
-// parts of 2561..4096 entries (none in text) and whatever a batch lists beyond k_lz2_find's grid: 256 looping workgroups, gone at
+// parts of 2049..4096 entries (none in text) and whatever a batch lists beyond k_lz2_find's grid: 256 looping workgroups, gone at
 // once when there is nothing to do.  Its own launch and — in the pipelined encoder — NOT on the stream of partition and find: an
 // empty launch still has to be given 76 KiB of LDS per workgroup before it can leave, and it waited about a millisecond per batch
 // for that behind the parse kernel of the batch before, on the one chain the pipeline is bound by (kernel timeline, round 4:

@@ -155,7 +155,7 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
             }
             return -1;
         };
-        // parts of at most LZ2_CAP_S entries (three workgroups of stage 2 per CU); where no certified cut lies that close — one
+        // parts of at most LZ2_CAP_S entries (four workgroups of stage 2 per CU); where no certified cut lies that close — one
         // cluster of more entries — a part of up to LZ2_CAP entries (k_lz2_find_wide: two per CU)
         while (n - cur > LZ2_CAP_S) {
             int32_t gr = cut_below(cur + LZ2_CAP_S);

@@ -9,6 +9,7 @@
 // dense occupancy bitmap held in LDS.  DESIGN.md has the argument and the measurements.
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 #define LZ_MAX_BLOCK   65536u
 #define LZ_TAIL        64u            // zero bytes the reference would read past the block end
@@ -181,17 +182,39 @@ __device__ __forceinline__ void lz_block_to_lds(uint8_t *s_dst, const uint8_t *_
     }
 }
 
-// ---- block-wide scans over 1024 threads (16 waves) -------------------------------------------
-template <typename T, typename Op>
-__device__ __forceinline__ T wave_inclusive_scan(T v, Op op)
+// DPP moves within the wave: a lane whose source lies outside the row / wave (or in a row the row mask leaves out) keeps
+// `old`.  Lane predicates never leave the DPP control, so nothing has to stay live in SGPRs between the scans of a kernel
+// (as ds_bpermute-based shuffles do: their lane compares are hoisted and kept as 64-bit masks).
+template <int CTRL, int ROW_MASK, typename T>
+__device__ __forceinline__ T dpp_move(T v, T old)
 {
-    const int lane = threadIdx.x & 63;
+    static_assert(sizeof(T) % 4 == 0, "32-bit words");
+    uint32_t w[sizeof(T) / 4], o[sizeof(T) / 4];
+    __builtin_memcpy(w, &v, sizeof(T));
+    __builtin_memcpy(o, &old, sizeof(T));
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T t = __shfl_up(v, o);
-        if (lane >= o) v = op(t, v);          // (earlier, later): the order matters for non-commutative operators —
-    }                                         // round 1 had op(v, t), which composed the partition's overflow maps backwards
-    return v;                                 // inside a wave and UNDER-estimated the carry behind a long run (mi_selftest_scan)
+    for (unsigned k = 0; k < sizeof(T) / 4; ++k)
+        w[k] = (uint32_t)__builtin_amdgcn_update_dpp((int)o[k], (int)w[k], CTRL, ROW_MASK, 0xF, false);
+    T r;
+    __builtin_memcpy(&r, w, sizeof(T));
+    return r;
+}
+
+// ---- block-wide scans over 1024 threads (16 waves) -------------------------------------------
+// inclusive scan of a full wave; `ident` is the identity of op (op(earlier, later): the order matters for non-commutative
+// operators — round 1 had op(later, earlier), which composed the partition's overflow maps backwards inside a wave and
+// UNDER-estimated the carry behind a long run (mi_selftest_scan)).  Rows of 16 lanes by row_shr 1, 2, 4, 8, then lane 15
+// of every row into the next one (row_bcast:15) and lane 31 into rows 2 and 3 (row_bcast:31).
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_inclusive_scan(T v, Op op, T ident)
+{
+    v = op(dpp_move<0x111, 0xF>(v, ident), v);
+    v = op(dpp_move<0x112, 0xF>(v, ident), v);
+    v = op(dpp_move<0x114, 0xF>(v, ident), v);
+    v = op(dpp_move<0x118, 0xF>(v, ident), v);
+    v = op(dpp_move<0x142, 0xA>(v, ident), v);
+    v = op(dpp_move<0x143, 0xC>(v, ident), v);
+    return v;
 }
 
 // exclusive scan across the block; `ident` is the identity; s_tmp needs nwaves+1 entries.
@@ -200,9 +223,8 @@ template <typename T, typename Op>
 __device__ __forceinline__ T block_exclusive_scan(T v, Op op, T ident, T *s_tmp, T *total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    T inc = wave_inclusive_scan(v, op);
-    T exc = __shfl_up(inc, 1);
-    if (lane == 0) exc = ident;
+    T inc = wave_inclusive_scan(v, op, ident);
+    T exc = dpp_move<0x138, 0xF>(inc, ident);             // wave_shr:1 — lane 0 keeps the identity
     if (lane == 63) s_tmp[wave] = inc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -254,7 +276,16 @@ struct OpAm { __device__ uint64_t operator()(uint64_t earlier, uint64_t later) c
 //   counted  the caller has zeroed the counters and counted already: cnt[digit * (NWAVES + 1) + i / radix_seg<NWAVES>(n)] for every
 //            input index i (it had the digits in hand: one pass over the input less)
 //   hook(j, e)  called for every element with the output index it was stored at (e.g. to count the NEXT pass's digits)
+//   counters are 32-bit, or 16-bit (CntRow of uint16_t: k_lz2_find, where a count is at most 2048 and LDS is short).  LDS has no
+//            16-bit add: a 16-bit counter is added to through the dword that holds it (4-byte aligned array), shifted into its
+//            half — a counter never carries into its neighbour, and a returning add still hands out slots in lane order.
 struct RadixNoHook { __device__ __forceinline__ void operator()(uint32_t, uint32_t) const {} };
+__device__ __forceinline__ uint32_t radix_cnt_add(uint32_t *cnt, uint32_t i, uint32_t v) { return atomicAdd(&cnt[i], v); }
+__device__ __forceinline__ uint32_t radix_cnt_add(uint16_t *cnt, uint32_t i, uint32_t v)
+{
+    const uint32_t sh = 16u * (i & 1u);
+    return (atomicAdd(reinterpret_cast<uint32_t *>(cnt) + (i >> 1), v << sh) >> sh) & 0xFFFFu;
+}
 template <int NWAVES> __device__ __forceinline__ uint32_t radix_seg(uint32_t n) { return ((n + (uint32_t)(NWAVES * 64) - 1u) / (uint32_t)(NWAVES * 64)) * 64u; }
 template <int D, bool SKIP = false> struct RadixDepth { static constexpr int value = D; static constexpr bool skip_identity = SKIP; };
 template <int NWAVES, int NBITS, typename E, typename CntRow, typename Load, typename Digit, typename Store, typename Hook = RadixNoHook, typename Depth = RadixDepth<1>>
@@ -263,11 +294,13 @@ __device__ __forceinline__ bool radix_pass(uint32_t n, CntRow *s_cnt, Load load,
 {
     long long tk_ = dbg ? clock64() : 0;
 #define RP_TICK(k) do { if (dbg && threadIdx.x == 0) { long long t2 = clock64(); atomicAdd((unsigned long long *)&dbg[k], (unsigned long long)(t2 - tk_)); tk_ = t2; } } while (0)
-    static_assert(sizeof(CntRow) / sizeof(uint32_t) >= (1u << NBITS), "counter row too narrow for the digit");
+    using C = std::remove_reference_t<decltype(s_cnt[0][0])>;
+    static_assert(std::is_same<C, uint32_t>::value || std::is_same<C, uint16_t>::value, "32- or 16-bit counters");
+    static_assert(sizeof(CntRow) / sizeof(C) >= (1u << NBITS), "counter row too narrow for the digit");
     constexpr int ND = 1 << NBITS;
     constexpr int NT = NWAVES * 64;
     constexpr int ST = NWAVES + 1;
-    uint32_t *cnt = &s_cnt[0][0];
+    C *cnt = &s_cnt[0][0];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t seg = ((n + (uint32_t)NT - 1u) / (uint32_t)NT) * 64u;
     const uint32_t a = wave * seg, b = (a + seg < n) ? a + seg : n;
@@ -293,8 +326,8 @@ __device__ __forceinline__ bool radix_pass(uint32_t n, CntRow *s_cnt, Load load,
                     const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)dg[u]);
                     const uint64_t live = __ballot(v);
                     if (__ballot(v && dg[u] != d0) == 0ull && (live & 1ull)) {               // (lane 0 is live: d0 is a live lane's digit)
-                        if (lane == 0) atomicAdd(&cnt[d0 * ST + wave], (uint32_t)__popcll(live));
-                    } else if (v) atomicAdd(&cnt[dg[u] * ST + wave], 1u);
+                        if (lane == 0) radix_cnt_add(cnt, d0 * ST + wave, (uint32_t)__popcll(live));
+                    } else if (v) radix_cnt_add(cnt, dg[u] * ST + wave, 1u);
                 }
             }
         } else
@@ -303,7 +336,7 @@ __device__ __forceinline__ bool radix_pass(uint32_t n, CntRow *s_cnt, Load load,
 #pragma unroll
             for (int u = 0; u < 4; ++u) dg[u] = (i + 64u * u < b) ? digit(load(i + 64u * u)) : 0u;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) if (i + 64u * u < b) atomicAdd(&cnt[dg[u] * ST + wave], 1u);
+            for (int u = 0; u < 4; ++u) if (i + 64u * u < b) radix_cnt_add(cnt, dg[u] * ST + wave, 1u);
         }
     }
     __syncthreads();
@@ -327,7 +360,7 @@ __device__ __forceinline__ bool radix_pass(uint32_t n, CntRow *s_cnt, Load load,
     const uint32_t base = block_exclusive_scan<uint32_t>(tid < ND ? tot : 0u, OpAddU32(), 0u, s_scan, &total);
     if (tid < ND) {
 #pragma unroll
-        for (int w = 0; w < NWAVES; ++w) cnt[tid * ST + w] = pre[w] + base;
+        for (int w = 0; w < NWAVES; ++w) cnt[tid * ST + w] = (C)(pre[w] + base);
     }
     __syncthreads();
     RP_TICK(9);
@@ -345,7 +378,7 @@ __device__ __forceinline__ bool radix_pass(uint32_t n, CntRow *s_cnt, Load load,
 #pragma unroll
             for (int u = 0; u < 4; ++u) { ee[u] = E{}; dg[u] = 0; if (i + 64u * u < b) { ee[u] = load(i + 64u * u); dg[u] = digit(ee[u]); } }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) sl[u] = (i + 64u * u < b) ? atomicAdd(&cnt[dg[u] * ST + wave], 1u) : 0u;
+            for (int u = 0; u < 4; ++u) sl[u] = (i + 64u * u < b) ? radix_cnt_add(cnt, dg[u] * ST + wave, 1u) : 0u;
 #ifdef MI_TEST_HOOKS                                       /* compiled only into lib_test/ (csrc/Makefile): the hook cost the shipped scatter 2.5 % */
             if (arank & LZP_BREAK) {
                 // test hook: what an out-of-order atomic would do — neighbours with one digit trade places (still a permutation)
@@ -390,7 +423,7 @@ __device__ __forceinline__ bool radix_pass(uint32_t n, CntRow *s_cnt, Load load,
                 const uint32_t rank = __popcll(below), num = __popcll(mask);
                 const int leader = __ffsll((unsigned long long)mask) - 1;
                 uint32_t old = 0;
-                if (valid && lane == leader) old = atomicAdd(&cnt[d * ST + wave], num);
+                if (valid && lane == leader) old = radix_cnt_add(cnt, d * ST + wave, num);
                 old = __shfl(old, leader < 0 ? 0 : leader);
                 if (valid) { store(old + rank, ee[u]); hook(old + rank, (uint32_t)ee[u]); }
             }
@@ -421,7 +454,7 @@ __device__ __forceinline__ bool radix_pass(uint32_t n, CntRow *s_cnt, Load load,
         const uint32_t rank = __popcll(below), num = __popcll(mask);
         const int leader = __ffsll((unsigned long long)mask) - 1;
         uint32_t old = 0;
-        if (valid && lane == leader) old = atomicAdd(&cnt[d * ST + wave], num);
+        if (valid && lane == leader) old = radix_cnt_add(cnt, d * ST + wave, num);
         old = __shfl(old, leader < 0 ? 0 : leader);
         if (valid) { store(old + rank, e); hook(old + rank, (uint32_t)e); }
     }

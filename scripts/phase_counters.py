@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """In-kernel phase shares of k_lz2_find / radix_pass / k_lz_parse_emit (clock64 counters, MI_LZ_DEBUG=1; development aid).
-    MI_LZ_DEBUG=1 python scripts/phase_counters.py [bytes]"""
+    MI_LZ_DEBUG=1 python scripts/phase_counters.py [bytes]
+k_lz2_find's counters (and the radix_pass counters inside it) exist in measurement builds only: make OUT=../lib_measure
+EXTRA=-DMI_MEASURE in compression_algorithms_amd/csrc, then MI_CODEC_LIB=.../lib_measure/libmi_codec.so; elsewhere they read 0."""
 import ctypes as C
 import os
 import sys
