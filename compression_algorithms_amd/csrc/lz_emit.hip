@@ -526,6 +526,16 @@ mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t
 uint32_t lz_batch_blocks(mi_ctx *ctx, uint64_t nblocks);
 
 void defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, hipStream_t s);
+// defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
+void defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
+                        uint32_t block, uint64_t b0, uint32_t nb, hipStream_t s);
+size_t    defz_ws_bytes();
+mi_status defz_check(const mi_lz_params *p, uint32_t container);
+mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t *base_bits,
+                     void *zws, hipStream_t s);
+mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
+                   void *zws, uint64_t *d_out_bytes, hipStream_t s);
+struct DefzCall { uint32_t container; uint64_t *d_out_bytes; };
 
 // lzw.hip: the lz77 flavour on blocks above 64 KiB
 size_t    lzw_scratch_bytes(uint32_t nb, uint32_t block);
@@ -541,16 +551,19 @@ mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_
                                    uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, bool *done);
 
 // mode_h = 0: the reference's token stream.  mode_h = 1: the same tokens, entropy coded per block (defh.hip); the
-// per-block records are word aligned, so the same scan / concatenate kernels place them.
+// per-block records are word aligned, so the same scan / concatenate kernels place them.  mode_h = 2 (z != nullptr): the
+// same tokens as standard DEFLATE records (defz.hip), byte aligned, placed behind the container header; the caller has
+// checked the parameters and the capacity.
 static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
-                                uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, int mode_h)
+                                uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, int mode_h,
+                                const DefzCall *z = nullptr)
 {
     if (!ctx || !d_out || !d_block_bits || (n && !d_in)) return MI_ERR_ARG;
     mi_status st = lz_check_params(p);
     if (st) return st;
     if (((uintptr_t)d_out & 3u) != 0) return MI_ERR_ARG;
-    if (mode_h && (!p->deflate || p->lbits > 5 || p->wbits > 16)) return MI_ERR_ARG;
-    if (cap_bytes < (mode_h ? mi_deflate_h_bound_bytes(n, p) : mi_lz_bound_bytes(n, p))) return MI_ERR_CAPACITY;
+    if (mode_h == 1 && (!p->deflate || p->lbits > 5 || p->wbits > 16)) return MI_ERR_ARG;
+    if (mode_h != 2 && cap_bytes < (mode_h ? mi_deflate_h_bound_bytes(n, p) : mi_lz_bound_bytes(n, p))) return MI_ERR_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
     const LzP P = lz_params_of(ctx, p);
     const uint64_t nblocks = (n + P.block - 1) / P.block;
@@ -592,13 +605,19 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
     const int nsets = overlap ? MI_SETS : 1;
     const size_t set_bytes = mi_align_up(lz_scratch_bytes(nbmax), 4096);
     const size_t trec_bytes = mode_h ? (size_t)nbmax * LZ_MAX_BLOCK * 4 : 0;       // token records, one array per set
-    st = mi_ws_reserve(ctx, set_bytes * nsets + 8192 + trec_bytes * nsets);
+    const size_t z_bytes = z ? defz_ws_bytes() : 0;                                  // mode Z: the checksum's partials
+    st = mi_ws_reserve(ctx, set_bytes * nsets + 8192 + trec_bytes * nsets + z_bytes);
     if (st) return st;
     LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS];
     for (int k = 0; k < nsets; ++k) lz_carve(ctx, nbmax, &sc[k], &sc2[k], k);
     uint64_t *base_bits = reinterpret_cast<uint64_t *>((uint8_t *)ctx->ws + set_bytes * nsets);
     uint32_t *trec_base = reinterpret_cast<uint32_t *>((uint8_t *)ctx->ws + set_bytes * nsets + 8192);
-    MI_HIP(ctx, hipMemsetAsync(base_bits, 0, 8, s));
+    void *zws = (uint8_t *)ctx->ws + set_bytes * nsets + 8192 + trec_bytes * nsets;
+    if (z) {
+        st = defz_begin(ctx, z->container, d_in, n, d_out, base_bits, zws, s);       // (the base starts at the header's bits)
+        if (st) return st;
+        if (nblocks == 0) return defz_end(ctx, z->container, d_out, d_block_bits, 0, n, zws, z->d_out_bytes, s);
+    } else MI_HIP(ctx, hipMemsetAsync(base_bits, 0, 8, s));
     if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return MI_OK; }
     hipStream_t sb = overlap ? ctx->side : s, sp = overlap ? ctx->parse : s;
     // stage C of one batch (set k): parse / emit (+ the entropy stage in mode H) / scan / concatenate
@@ -609,9 +628,12 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
             mi_prof_scope pr(ctx, "k_lz_parse_emit", sp, (uint64_t)nb * P.block);
             hipLaunchKernelGGL(k_lz_parse_emit, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
         }
-        if (mode_h) {
+        if (mode_h == 1) {
             mi_prof_scope ph(ctx, "k_defh_encode", sp, (uint64_t)nb * P.block);
             defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, sp);
+        } else if (mode_h == 2) {
+            mi_prof_scope ph(ctx, "k_defz_encode", sp, (uint64_t)nb * P.block);
+            defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp);
         }
         hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, sp, sc[k].block_bits, nb, base_bits, excl_local, d_block_bits + b0);
         {
@@ -727,6 +749,7 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
         MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_fork, 0));
     }
     MI_HIP(ctx, hipGetLastError());
+    if (z) return defz_end(ctx, z->container, d_out, d_block_bits, nblocks, n, zws, z->d_out_bytes, s);
     return MI_OK;
 }
 
@@ -740,6 +763,17 @@ extern "C" mi_status mi_deflate_h_encode_dev(mi_ctx *ctx, const mi_lz_params *p,
                                              uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream)
 {
     return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, 1);
+}
+
+extern "C" mi_status mi_deflate_z_encode_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, const uint8_t *d_in, uint64_t n,
+                                             uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, uint64_t *d_out_bytes, void *stream)
+{
+    if (!ctx || !d_out || !d_block_bits || !d_out_bytes || (n && !d_in)) return MI_ERR_ARG;
+    mi_status st = defz_check(p, container);
+    if (st) return st;
+    if (cap_bytes < mi_deflate_z_bound_bytes(n, p, container)) return MI_ERR_CAPACITY;
+    const DefzCall z{container, d_out_bytes};
+    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, 2, &z);
 }
 
 mi_status mi_encode_again_if_unstable(mi_ctx *ctx, uint32_t seen_before, mi_status st, mi_status (*again)(void *), void *arg);     // host_api.hip

@@ -182,3 +182,93 @@ def decompress_whole(stream, ctx=None):
                                         stream.total_bits, C.c_void_p(out.data_ptr()), stream.n, ctx.stream_ptr())
     _lib.check(st, "mi_lz77_whole_decode_dev")
     return out[: stream.n]
+
+
+# ---- mode Z: standard DEFLATE (RFC 1951) in a raw / zlib / gzip container (include/mi_codec.h) -------------------
+CONTAINERS = {"raw": 0, "zlib": 1, "gzip": 2}
+
+
+class ZStream:
+    """A mode-Z stream on the device: `data` uint8 tensor, `block_bits` int64 tensor [nblocks+1] (bit offset of every
+    record, the container header included; the last entry is where the closing 03 00 starts), `n` input bytes."""
+
+    def __init__(self, data, block_bits, out_bytes, n, p, container, ctx=None, violations_before=0):
+        self.data, self.block_bits, self._out_bytes, self.n, self.p = data, block_bits, out_bytes, n, p
+        self.container = container
+        self._ctx, self._v0 = ctx, violations_before
+
+    @property
+    def nbytes(self):
+        b = int(self._out_bytes.item())                    # (synchronises: the encoder has joined torch's stream)
+        if self._ctx is not None and self._ctx.order_violations() != self._v0:
+            self._v0 = self._ctx.order_violations()
+            raise _lib.MiError(10, "the encoder that wrote this stream reported a sort out of order")
+        return b
+
+    def tobytes(self):
+        return self.data[: self.nbytes].cpu().numpy().tobytes()
+
+
+def bound_bytes_z(n, p=None, container="gzip"):
+    """mi_deflate_z_bound_bytes"""
+    p = p or params("deflate")
+    c = CONTAINERS.get(container, container)
+    return int(_lib.lib().mi_deflate_z_bound_bytes(n, C.byref(p), c))
+
+
+def compress_z(data, p=None, container="gzip", ctx=None, cap=None):
+    """The reference's deflate tokens as standard DEFLATE that zlib.decompress / gzip.decompress read: one byte-aligned
+    record per p.block input bytes, in container "raw" (RFC 1951), "zlib" (RFC 1950) or "gzip" (RFC 1952)."""
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    c = CONTAINERS.get(container, container)
+    d_in = as_device_bytes(data, ctx.device)
+    n = d_in.numel()
+    nblocks = (n + p.block - 1) // p.block if p.block else 0
+    if cap is None:
+        cap = bound_bytes_z(n, p, c) if c in CONTAINERS.values() else 64
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=ctx.device)
+    bits = torch.zeros(nblocks + 2, dtype=torch.int64, device=ctx.device)
+    v0 = ctx.order_violations()
+    st = ctx.L.mi_deflate_z_encode_dev(ctx.h, C.byref(p), c, C.c_void_p(d_in.data_ptr() if n else 0), n, C.c_void_p(out.data_ptr()),
+                                       cap, C.c_void_p(bits.data_ptr()), C.c_void_p(bits[nblocks + 1:].data_ptr()), ctx.stream_ptr())
+    _lib.check(st, "mi_deflate_z_encode_dev")
+    return ZStream(out, bits[: nblocks + 1], bits[nblocks + 1:], n, p, c, ctx, v0)
+
+
+def compress_z_host(data, p=None, container="gzip", ctx=None):
+    """the host-buffer entry point (mi_deflate_z_encode) -> (bytes, block table as a list)"""
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    c = CONTAINERS.get(container, container)
+    buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+    n = buf.size
+    nblocks = (n + p.block - 1) // p.block
+    cap = bound_bytes_z(n, p, c)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    bits = np.zeros(nblocks + 1, dtype=np.uint64)
+    nb = C.c_uint64(0)
+    st = ctx.L.mi_deflate_z_encode(ctx.h, C.byref(p), c, buf.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p), cap,
+                                   bits.ctypes.data_as(C.c_void_p), C.byref(nb))
+    _lib.check(st, "mi_deflate_z_encode")
+    return out[: nb.value].tobytes(), [int(x) for x in bits]
+
+
+def _checksum(fn, data, ctx):
+    ctx = ctx or default_context()
+    d_in = as_device_bytes(data, ctx.device)
+    n = d_in.numel()
+    res = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+    st = getattr(ctx.L, fn)(ctx.h, C.c_void_p(d_in.data_ptr() if n else 0), n, C.c_void_p(res.data_ptr()), ctx.stream_ptr())
+    _lib.check(st, fn)
+    return int(res.item()) & 0xFFFFFFFF
+
+
+def crc32(data, ctx=None):
+    """CRC-32 of the buffer on the GPU (the value zlib.crc32 gives)"""
+    return _checksum("mi_crc32_dev", data, ctx)
+
+
+def adler32(data, ctx=None):
+    """Adler-32 of the buffer on the GPU (the value zlib.adler32 gives)"""
+    return _checksum("mi_adler32_dev", data, ctx)

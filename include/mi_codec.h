@@ -273,6 +273,54 @@ mi_status mi_deflate_h_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t 
                               const uint64_t *h_block_bits, uint8_t *h_out, uint64_t n);
 
 /* ------------------------------------------------------------------------------------
+ * Deflate "mode Z": standard DEFLATE (RFC 1951), raw or in a zlib (RFC 1950) / gzip (RFC 1952)
+ * container — what zlib's inflate, gzip -d and HTTP stacks read.
+ *
+ * Tokens: per input block of p->block bytes exactly the token sequence of mi_lz_encode_dev
+ * (deflate flavour: same finder, same parse, fresh table per block), with one change: a last
+ * match that runs past the block end (A.3.4) is clipped to L' = block_end - pos, a match of L'
+ * if L' >= 3, else L' literals read from the input.  Lengths -> codes 257..285, distances ->
+ * codes 0..29, with their extra bits.
+ * One RECORD per input block: DEFLATE blocks with BFINAL = 0 coding exactly that block, then an
+ * empty stored block (3 header bits, padding to a byte, 00 00 FF FF: a sync flush), so a record is
+ * whole bytes, starts on a byte boundary and never refers to an earlier block.  The block type is
+ * the shortest in bits of dynamic Huffman (BTYPE 10), fixed Huffman (01) and stored (00), ties in
+ * that order, all three sized exactly from the histograms; a stored block of 65 536 bytes is two
+ * stored blocks (LEN <= 65 535).  Codes: literal/length and distance lengths <= 15, code-length
+ * lengths <= 7, every code complete; a code with fewer than two used symbols is padded to two codes
+ * of length 1 as zlib pads it; end-of-block is always coded; the code lengths are run-length coded
+ * with 16/17/18.  The stream ends with 03 00 (a final fixed block with only end-of-block); for
+ * n = 0 the raw stream is just 03 00.
+ * Containers: MI_CONTAINER_RAW the above; MI_CONTAINER_ZLIB 78 9C, the raw stream, Adler-32
+ * big-endian; MI_CONTAINER_GZIP 1F 8B 08 00 00 00 00 00 00 FF (no flags, MTIME 0, OS 255: the
+ * output is reproducible), the raw stream, CRC-32 little-endian, ISIZE = n mod 2^32 little-endian.
+ * d_block_bits u64[nblocks+1]: entry b is the bit offset in d_out where record b starts (the
+ * container header included, so entry 0 is 0, 16 or 80; all multiples of 8); entry nblocks is where
+ * the final 03 00 starts.  Every record can be inflated on its own from there: restart points.
+ * *d_out_bytes: the total length in bytes (on the device, like the table).
+ * p: deflate flavour with wbits <= 15, lbits <= 8, block <= 65 536; anything else, or an unknown
+ * container, is MI_ERR_ARG.  d_out 4-byte aligned; cap_bytes below mi_deflate_z_bound_bytes is
+ * MI_ERR_CAPACITY.
+ * ------------------------------------------------------------------------------------ */
+#define MI_CONTAINER_RAW  0u
+#define MI_CONTAINER_ZLIB 1u
+#define MI_CONTAINER_GZIP 2u
+/* per block of b bytes b + 5 ceil(b / 65535) + 5 (the stored form and its sync flush), plus the container's header and
+ * trailer (raw 0, zlib 2 + 4, gzip 10 + 8) and the closing 03 00 */
+uint64_t  mi_deflate_z_bound_bytes(uint64_t n, const mi_lz_params *p, uint32_t container);
+mi_status mi_deflate_z_encode_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, const uint8_t *d_in, uint64_t n,
+                                  uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, uint64_t *d_out_bytes, void *stream);
+/* host buffers: copy in, encode, copy out; h_block_bits u64[nblocks+1]; *h_out_bytes (may be NULL) = bytes written */
+mi_status mi_deflate_z_encode(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, const uint8_t *h_in, uint64_t n,
+                              uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, uint64_t *h_out_bytes);
+/* the checksums of the containers on their own (zlib's crc32 / adler32 of the whole buffer), asynchronous on `stream`:
+ * per-workgroup partials, then one combine step; the result is one u32 on the device.  The partials live in the context
+ * workspace like every encoder's scratch (8 KiB): one call of a context in flight at a time, as for the encoders.
+ * Inside mi_deflate_z_encode_dev the checksum runs on `stream` ahead of the LZ pipeline (~0.5 ms for 10^9 bytes). */
+mi_status mi_crc32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_crc, void *stream);
+mi_status mi_adler32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_adler, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is
  * defined by this build).  Record layout in include/mi_fse.h.
  * ------------------------------------------------------------------------------------ */
