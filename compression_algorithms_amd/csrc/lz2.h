@@ -98,6 +98,10 @@ struct Lz2Scratch {
     uint16_t     *bigpos, *bigrs, *bigpid, *bigcand; // [nb][LZ2_BIG_STRIDE] entries of exported clusters, (cluster, time) order
     Lz2BigDesc   *desc[LZ2_NCLASS];                  // per class: [nb * capacity of the class]
     uint32_t     *big_count;                         // [LZ2_NCLASS]
+    // the lane classes (7, 0, 1, 2: clusters of 8..127 entries) as ONE list sorted by size, longest first (k_lz2_lane_count /
+    // k_lz2_lane_place, replayed by k_lz2_lanes): {block, start, count, anom | limit << 16 (0xFFFF: none)} per cluster
+    uint4        *lane_list;                         // [nb * lz2_class_cap(7)]: a block holds at most 65536 / 8 such clusters
+    uint32_t     *lane_hist;                         // [LZ2_WAVE] clusters per size, then [LZ2_WAVE] placement cursors (zeroed by stage 1)
     uint64_t     *dbg;                               // phase cycle counters (MI_LZ_DEBUG=1), else NULL
     uint32_t      wave_min;                          // see lz2_class_of
     uint32_t      stop_phase;                        // measurement only (MI_LZ_STOP_PHASE=k): k_lz2_find leaves after phase k; 0 = run everything

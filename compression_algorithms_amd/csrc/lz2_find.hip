@@ -13,6 +13,8 @@
 //                       - larger mixed ones are exported on 16-byte boundaries, by size class.
 //   k_lz2_mid_direct  lane per exported cluster of 8..127 entries (64 clusters per wave, LDS regions per lane),
 //                     eight entries per load.
+//   k_lz2_lanes       the same replay in ONE launch (default; k_lz2_mid_direct with MI_LZ_LANES=0): the clusters sorted by size
+//                     (k_lz2_lane_count / k_lz2_lane_place), a wave per group of clusters of one size, regions sized by it.
 //   k_lz2_big         one WAVE per exported cluster of 512..1024 entries (and of what the row replay leaves): occupancy bitmap in
 //                     registers, first fit by ballot + v_readlane, 6 bytes of LDS per entry; bound by scalar-instruction issue.
 //   k_lz2_rows        FOUR exported clusters of 128..511 entries per wave, one per 16-lane row, 256..511 first (round 4).
@@ -1108,6 +1110,177 @@ void k_lz2_mid_direct(LzP P, Lz2Scratch sc, int cls)
     }
 }
 
+// =============================================================================================
+// The lane classes in one launch (round 6).  The exported clusters of 8..127 entries become ONE list sorted by size, longest
+// first (a counting sort over the sizes: k_lz2_lane_count, k_lz2_lane_place); k_lz2_lanes gives a wave clusters of ONE size,
+// as many as its LDS budget holds (at most 64), every lane's region sized by that size: n + 1 occupant dwords, ceil((n + 1) / 32)
+// bitmap words, n slot bytes, rounded up to an odd number of dwords (the regions of the lanes start on different banks, as the
+// odd stride of k_lz2_mid_direct did).  No lane idles behind a longer cluster, and a wave of 64-entry clusters holds twice the
+// lanes of k_lz2_mid_direct<128, 48>.  Waves are numbered long clusters first; the dispatcher hands them out in that order.
+// =============================================================================================
+constexpr uint32_t LANE_SIZES = LZ2_WAVE;                  // sizes 0..127 (8..127 occur)
+
+__host__ __device__ __forceinline__ uint32_t lz2_lane_region(uint32_t n)      // dwords of the region of an n-entry cluster: odd
+{
+    return ((n + 1u) + ((n + 32u) >> 5) + ((n + 3u) >> 2)) | 1u;
+}
+__host__ __device__ __forceinline__ uint32_t lz2_lane_width(uint32_t n, uint32_t budget_dw)    // clusters per wave of n-entry clusters
+{
+    const uint32_t l = budget_dw / lz2_lane_region(n);
+    return l < 64u ? l : 64u;
+}
+
+// descriptor v of the four lane classes taken as one array: 8..15 (class 7), 16..31 (0), 32..63 (1), 64..127 (2) entries
+__device__ __forceinline__ const Lz2BigDesc *lz2_lane_desc(const Lz2Scratch &sc, uint32_t v, uint32_t n7, uint32_t n0, uint32_t n1)
+{
+    if (v < n7) return sc.desc[7] + v;
+    v -= n7;
+    if (v < n0) return sc.desc[0] + v;
+    v -= n0;
+    if (v < n1) return sc.desc[1] + v;
+    return sc.desc[2] + (v - n1);
+}
+
+// clusters per size: LDS counters per workgroup, one global add per size
+__global__ __launch_bounds__(256)
+void k_lz2_lane_count(Lz2Scratch sc)
+{
+    __shared__ uint32_t s_h[LANE_SIZES];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n7 = sc.big_count[7], n0 = sc.big_count[0], n1 = sc.big_count[1], N = n7 + n0 + n1 + sc.big_count[2];
+    if (blockIdx.x * 256u >= N) return;
+    if (tid < LANE_SIZES) s_h[tid] = 0;
+    __syncthreads();
+    for (uint32_t v = blockIdx.x * 256u + tid; v < N; v += gridDim.x * 256u)
+        atomicAdd(&s_h[lz2_lane_desc(sc, v, n7, n0, n1)->count & (LANE_SIZES - 1u)], 1u);
+    __syncthreads();
+    if (tid < LANE_SIZES && s_h[tid]) atomicAdd(&sc.lane_hist[tid], s_h[tid]);
+}
+
+// the sorted list: a workgroup counts its descriptors per size, reserves a range of every size's bucket with one global add per
+// size and ranks inside it by LDS atomics (the order inside a size does not matter: the clusters are independent)
+__global__ __launch_bounds__(256)
+void k_lz2_lane_place(LzP P, Lz2Scratch sc)
+{
+    __shared__ uint32_t s_h[LANE_SIZES], s_at[LANE_SIZES];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n7 = sc.big_count[7], n0 = sc.big_count[0], n1 = sc.big_count[1], N = n7 + n0 + n1 + sc.big_count[2];
+    if (blockIdx.x * 256u >= N) return;
+    if (tid < LANE_SIZES) s_h[tid] = 0;
+    __syncthreads();
+    for (uint32_t v = blockIdx.x * 256u + tid; v < N; v += gridDim.x * 256u)
+        atomicAdd(&s_h[lz2_lane_desc(sc, v, n7, n0, n1)->count & (LANE_SIZES - 1u)], 1u);
+    __syncthreads();
+    if (tid < 64u) {
+        // size c's bucket starts behind every cluster of more than c entries; lane l holds sizes 127 - 2l and 126 - 2l
+        const uint32_t a = LANE_SIZES - 1u - 2u * tid, b = a - 1u;
+        const uint32_t ha = sc.lane_hist[a], hb = sc.lane_hist[b];
+        const uint32_t before = wave_inclusive_scan<uint32_t>(ha + hb, OpAddU32(), 0u) - ha - hb;
+        if (s_h[a]) s_at[a] = before + atomicAdd(&sc.lane_hist[LANE_SIZES + a], s_h[a]);
+        if (s_h[b]) s_at[b] = before + ha + atomicAdd(&sc.lane_hist[LANE_SIZES + b], s_h[b]);
+        s_h[a] = 0; s_h[b] = 0;
+    }
+    __syncthreads();
+    for (uint32_t v = blockIdx.x * 256u + tid; v < N; v += gridDim.x * 256u) {
+        const Lz2BigDesc *dp = lz2_lane_desc(sc, v, n7, n0, n1);
+        const uint32_t c = dp->count & (LANE_SIZES - 1u), at = s_at[c] + atomicAdd(&s_h[c], 1u);
+        if (at >= N) { lz_order_violation(P); continue; }             // (the counts are those k_lz2_lane_count saw: never)
+        sc.lane_list[at] = make_uint4(dp->block, dp->start, dp->count, (dp->anom & 0xFFFFu) | (dp->limit << 16));
+    }
+}
+
+// Wave g of the launch replays clusters of one size n in [size_lo, size_hi], the waves of size 127 first.  budget_dw = dynamic
+// LDS of the launch in dwords (>= lz2_lane_region(127)).  The step body is that of k_lz2_mid_direct.
+__global__ __launch_bounds__(64)
+void k_lz2_lanes(LzP P, Lz2Scratch sc, uint32_t size_hi, uint32_t size_lo, uint32_t budget_dw)
+{
+    extern __shared__ uint32_t s_lane[];
+    const uint32_t lane = threadIdx.x;
+    // lane l: sizes a = 127 - 2l and a - 1, their clusters (for the list offsets: all sizes) and this launch's waves of them
+    const uint32_t a = LANE_SIZES - 1u - 2u * lane, b = a - 1u;
+    const uint32_t ha = sc.lane_hist[a], hb = sc.lane_hist[b];
+    const uint32_t wa = (a <= size_hi && a >= size_lo) ? (ha + lz2_lane_width(a, budget_dw) - 1u) / lz2_lane_width(a, budget_dw) : 0u;
+    const uint32_t wb = (b <= size_hi && b >= size_lo) ? (hb + lz2_lane_width(b, budget_dw) - 1u) / lz2_lane_width(b, budget_dw) : 0u;
+    const uint32_t hin = wave_inclusive_scan<uint32_t>(ha + hb, OpAddU32(), 0u);
+    const uint32_t win = wave_inclusive_scan<uint32_t>(wa + wb, OpAddU32(), 0u);
+    const uint32_t g = blockIdx.x;
+    if (g >= (uint32_t)__builtin_amdgcn_readlane((int)win, 63)) return;
+    // the lane whose sizes hold wave g: the lanes whose waves all lie below g come first
+    const uint32_t j = (uint32_t)__popcll(__ballot(win <= g));
+    const uint32_t wj = (uint32_t)__builtin_amdgcn_readlane((int)win, (int)j), waj = (uint32_t)__builtin_amdgcn_readlane((int)wa, (int)j),
+                   wbj = (uint32_t)__builtin_amdgcn_readlane((int)wb, (int)j), hj = (uint32_t)__builtin_amdgcn_readlane((int)hin, (int)j),
+                   haj = (uint32_t)__builtin_amdgcn_readlane((int)ha, (int)j), hbj = (uint32_t)__builtin_amdgcn_readlane((int)hb, (int)j);
+    const uint32_t q0 = g - (wj - waj - wbj);
+    const bool upper = q0 < waj;
+    const uint32_t n = LANE_SIZES - 1u - 2u * j - (upper ? 0u : 1u), q = upper ? q0 : q0 - waj, hn = upper ? haj : hbj;
+    const uint32_t first = (hj - haj - hbj) + (upper ? 0u : haj);        // clusters of more than n entries
+    const uint32_t width = lz2_lane_width(n, budget_dw), k0 = q * width, nl = (hn - k0 < width) ? hn - k0 : width;
+    uint4 dv = make_uint4(0u, 0u, 0u, 0xFFFFFFFFu);
+    if (lane < nl) dv = sc.lane_list[first + k0 + lane];
+    // every cluster of the wave has n entries (the list is sorted): anything else would overrun its region
+    if (lane < nl && dv.z != n) lz_order_violation(P);
+    const uint32_t cnt = (lane < nl && dv.z == n) ? n : 0u, W = 1u << P.wbits;
+    const uint32_t anom = (dv.w & 0xFFFFu) == 0xFFFFu ? ~0u : (dv.w & 0xFFFFu), limit = (dv.w >> 16) == 0xFFFFu ? ~0u : (dv.w >> 16);
+    const uint4 *vp = reinterpret_cast<const uint4 *>(sc.bigpos + (size_t)dv.x * LZ2_BIG_STRIDE + dv.y);
+    const uint4 *vr = reinterpret_cast<const uint4 *>(sc.bigrs + (size_t)dv.x * LZ2_BIG_STRIDE + dv.y);
+    const uint4 *vi = reinterpret_cast<const uint4 *>(sc.bigpid + (size_t)dv.x * LZ2_BIG_STRIDE + dv.y);
+    uint4 *vc = reinterpret_cast<uint4 *>(sc.bigcand + (size_t)dv.x * LZ2_BIG_STRIDE + dv.y);
+    uint32_t *occ = s_lane + (cnt ? lane : 0u) * lz2_lane_region(n);      // idle lanes (cnt = 0) touch nothing
+    uint32_t *bits = occ + (n + 1u);
+    uint8_t *slot = reinterpret_cast<uint8_t *>(bits + ((n + 32u) >> 5));
+    if (cnt) for (uint32_t k = 0; k < ((n + 32u) >> 5); ++k) bits[k] = 0;
+    const uint4 zero4 = make_uint4(0, 0, 0, 0);
+    uint4 evw = zero4;                                     // positions of entries [ev & ~7, +8): the next to retire
+    if (cnt) evw = vp[0];
+    uint32_t ev = 0, ev_p = evw.x & 0xFFFFu;
+    bool anom_pending = anom != ~0u;
+    const bool plain = anom == ~0u && limit == ~0u;        // not the cluster that covers bucket 0 / T
+    uint4 np = evw, nr = zero4, ni = zero4;                // the group after the current one is in flight
+    if (cnt) { nr = vr[0]; ni = vi[0]; }
+    for (uint32_t i0 = 0; i0 < n; i0 += 8) {
+        const uint4 cp = np, cr = nr, cid = ni;
+        if (i0 + 8 < cnt) { np = vp[(i0 >> 3) + 1]; nr = vr[(i0 >> 3) + 1]; ni = vi[(i0 >> 3) + 1]; }
+        uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t i = i0 + k;
+            if (i < cnt) {
+                const uint32_t p = u16_of(cp, k), r = u16_of(cr, k), id = u16_of(cid, k);
+                while (ev < i && ev_p + W < p) {           // FIFO retirement
+                    const uint32_t sb = slot[ev];
+                    bits[sb >> 5] &= ~(1u << (sb & 31u));
+                    ++ev;
+                    if ((ev & 7u) == 0) evw = vp[ev >> 3];
+                    ev_p = u16_of(evw, ev & 7u);
+                }
+                if (anom_pending && p > W - 1u) { bits[anom >> 5] &= ~(1u << (anom & 31u)); anom_pending = false; }
+                uint32_t wi = r >> 5;
+                const uint32_t w0 = bits[wi];
+                uint32_t res = LZ_NONE16;
+                if (plain && ev == 0) {                    // nothing evicted yet: find() = the word's first occurrence,
+                    if (id != p) res = id;                 // which is what the word id is (k_lz2_find, the sweep)
+                } else if (id != p && ((w0 >> (r & 31u)) & 1u)) {       // (a word's first occurrence in the block finds nothing, ever)
+                    for (uint32_t sb = r;; ++sb) {
+                        if (sb != r) {
+                            if (sb == limit && r < limit) break;
+                            if (!((bits[sb >> 5] >> (sb & 31u)) & 1u)) break;
+                        }
+                        const uint32_t o = occ[sb];
+                        if ((o & 0xFFFFu) == id) { res = o >> 16; break; }
+                    }
+                }
+                { const uint32_t v = res << ((k & 1u) * 16u); if (k < 2) o0 |= v; else if (k < 4) o1 |= v; else if (k < 6) o2 |= v; else o3 |= v; }
+                uint32_t wv = w0 | ((1u << (r & 31u)) - 1u);
+                while (wv == 0xFFFFFFFFu) wv = bits[++wi];
+                const uint32_t sb = (wi << 5) + (uint32_t)__builtin_ctz(~wv);
+                bits[sb >> 5] |= 1u << (sb & 31u);
+                occ[sb] = id | (p << 16); slot[i] = (uint8_t)sb;
+            }
+        }
+        if (i0 < cnt) vc[i0 >> 3] = make_uint4(o0, o1, o2, o3);      // pads of the last group: 0 (= skipped, lz2.h)
+    }
+}
+
 // lists -> by-position array (test hook mi_lz_find_all_dev and the fallback boundary)
 __global__ __launch_bounds__(1024)
 void k_lz2_scatter(Lz2Scratch sc, uint16_t *__restrict__ cand_by_pos /* [nb][65536] */)
@@ -1150,7 +1323,8 @@ size_t lz2_scratch_bytes(uint32_t nb)
 {
     size_t descs = 0;                                    // what lz2_carve takes for the class descriptor arrays, exactly
     for (uint32_t c = 0; c < LZ2_NCLASS; ++c) descs += lz2_class_cap(c);
-    return (size_t)nb * (LZ_MAX_BLOCK * (2 * 2 + 1) + LZ2_BIG_STRIDE * 2 * 4 + sizeof(Lz2BlockMeta) + 4 + 8 * LZ2_MAXPARTS + descs * sizeof(Lz2BigDesc)) + 16 * 256 + 4096 + 64 * 256;
+    return (size_t)nb * (LZ_MAX_BLOCK * (2 * 2 + 1) + LZ2_BIG_STRIDE * 2 * 4 + sizeof(Lz2BlockMeta) + 4 + 8 * LZ2_MAXPARTS + descs * sizeof(Lz2BigDesc)
+                         + lz2_class_cap(7) * sizeof(uint4)) + 16 * 256 + 4096 + 64 * 256 + 2 * LANE_SIZES * 4 + 256;
 }
 
 void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
@@ -1159,7 +1333,7 @@ void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
     sc->plist = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
     sc->cand = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
     sc->meta = cv.take<Lz2BlockMeta>(nb);
-    sc->fallback_count = cv.take<uint32_t>(64);
+    sc->fallback_count = cv.take<uint32_t>(64 + 2 * LANE_SIZES);
     sc->fallback_list = cv.take<uint32_t>(nb);
     sc->bigpos = cv.take<uint16_t>((size_t)nb * LZ2_BIG_STRIDE);
     sc->bigrs = cv.take<uint16_t>((size_t)nb * LZ2_BIG_STRIDE);
@@ -1168,8 +1342,10 @@ void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
     for (uint32_t c = 0; c < LZ2_NCLASS; ++c) sc->desc[c] = cv.take<Lz2BigDesc>((size_t)nb * lz2_class_cap(c));
     sc->big_count = sc->fallback_count + 16;
     sc->work_count = sc->fallback_count + 32;            // zeroed with the other counters by stage 1
+    sc->lane_hist = sc->fallback_count + 64;             // (as are these)
     sc->work = cv.take<uint64_t>((size_t)nb * LZ2_MAXPARTS);
     sc->work_slots = nb * LZ2_MAXPARTS;
+    sc->lane_list = cv.take<uint4>((size_t)nb * lz2_class_cap(7));
     sc->dbg = getenv("MI_LZ_DEBUG") ? cv.take<uint64_t>(64) : nullptr;
     // bits 16..: the row replay's switch (MI_LZ_ROWS, lz2_stage_b): with it the wave classes are three (128..255 apart)
     { const char *e = getenv("MI_LZ_ROWS"); const uint32_t rows = e ? (uint32_t)atoi(e) : 1u; sc->wave_min = LZ2_WAVE | ((rows ? 1u : 0u) << 16); }
@@ -1202,7 +1378,7 @@ void lz2_launch_partition(const uint8_t *d_in, uint64_t n, const LzP &P, const L
 mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                               const Lz2Scratch &sc, hipStream_t s)
 {
-    MI_HIP(ctx, hipMemsetAsync(sc.fallback_count, 0, 256, s));      // fallback_count and big_count[]
+    MI_HIP(ctx, hipMemsetAsync(sc.fallback_count, 0, (64 + 2 * LANE_SIZES) * 4, s));      // fallback_count, big_count[], lane_hist[]
     if (sc.dbg && ctx->lz_dbg != sc.dbg) { ctx->lz_dbg = sc.dbg; MI_HIP(ctx, hipMemsetAsync(sc.dbg, 0, 512, s)); }
     mi_prof_scope p(ctx, "k_lz2_partition", s, (uint64_t)nb * P.block);
     lz2_launch_partition(d_in, n, P, sc, block0, nb, s);
@@ -1253,7 +1429,7 @@ mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, ui
 }
 
 // stage B: replay of the exported clusters (almost no LDS: runs beside the next batch's stage A)
-// which: 1 = the lane replays of 8..31-entry clusters, 4 = of 32..127-entry clusters, 2 = the wave / row replays; 7 = all on `s`
+// which: 1 = the lane replays of 8..31-entry clusters, 4 = of 32..127-entry clusters (with k_lz2_lanes: all of them), 2 = the wave / row replays; 7 = all on `s`
 mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which)
 {
     // Replay grids cover the worst case and the kernels stride, so any grid is correct.  MI_LZ_REPLAY_WAVES=k caps them at
@@ -1266,13 +1442,31 @@ mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &
         const uint64_t g = (uint64_t)ncu * lz2_env_u32("MI_LZ_REPLAY_WAVES", 0);             // 0 = the worst-case grid
         return (uint32_t)((g == 0 || worst < g) ? (worst ? worst : 1) : g);
     };
-    if (which & 1) {
+    // the lane classes: ordering pass + ONE launch of k_lz2_lanes (one-batch calls: on the stream of `which & 4`); MI_LZ_LANES=0:
+    // the four per-class launches of k_lz2_mid_direct (A/B).  MI_LZ_LANES_KIB: LDS per wave of k_lz2_lanes (A/B).
+    static const bool lanes = !(getenv("MI_LZ_LANES") && getenv("MI_LZ_LANES")[0] == '0');
+    if (lanes && (which & 4)) {
+        static const uint32_t kib_env = lz2_env_u32("MI_LZ_LANES_KIB", 8);
+        const uint32_t kib = kib_env < 1u ? 1u : kib_env > 32u ? 32u : kib_env, budget_dw = kib * 256u;    // >= lz2_lane_region(127)
+        const uint64_t worst = (uint64_t)nb * lz2_class_cap(7);                  // lane-class clusters of the batch, at most
+        const uint32_t og = (uint32_t)((worst + 255u) / 256u < (uint64_t)ncu * 4u ? (worst + 255u) / 256u : (uint64_t)ncu * 4u);
+        { mi_prof_scope p(ctx, "k_lz2_lane_order", s, (uint64_t)nb * P.block);
+          hipLaunchKernelGGL(k_lz2_lane_count, dim3(og), dim3(256), 0, s, sc);
+          hipLaunchKernelGGL(k_lz2_lane_place, dim3(og), dim3(256), 0, s, P, sc); }
+        // waves: sum over the sizes of ceil(clusters / width) <= the batch's entries / min(size * width) + one partial wave per size
+        uint32_t m = ~0u;
+        for (uint32_t c = LZ2_BIG; c < LANE_SIZES; ++c) { const uint32_t x = c * lz2_lane_width(c, budget_dw); m = x < m ? x : m; }
+        const uint64_t waves = (uint64_t)nb * LZ_MAX_BLOCK / m + LANE_SIZES;
+        { mi_prof_scope p(ctx, "k_lz2_lanes", s, (uint64_t)nb * P.block);
+          hipLaunchKernelGGL(k_lz2_lanes, dim3((uint32_t)waves), dim3(64), budget_dw * 4u, s, P, sc, LANE_SIZES - 1u, LZ2_BIG, budget_dw); }
+    }
+    if (!lanes && (which & 1)) {
     { mi_prof_scope p(ctx, "k_lz2_mid<16>", s, (uint64_t)nb * P.block);
       hipLaunchKernelGGL((k_lz2_mid_direct<16, 64>), dim3(grid_of((uint64_t)nb * lz2_class_cap(7) / 64 + 1)), dim3(64), 0, s, P, sc, 7); }
     { mi_prof_scope p(ctx, "k_lz2_mid<32>", s, (uint64_t)nb * P.block);
       hipLaunchKernelGGL((k_lz2_mid_direct<32, 64>), dim3(grid_of((uint64_t)nb * lz2_class_cap(0) / 64 + 1)), dim3(64), 0, s, P, sc, 0); }
     }
-    if (which & 4) {
+    if (!lanes && (which & 4)) {
     { mi_prof_scope p(ctx, "k_lz2_mid<64>", s, (uint64_t)nb * P.block);
       hipLaunchKernelGGL((k_lz2_mid_direct<64, 64>), dim3(grid_of((uint64_t)nb * lz2_class_cap(1) / 64 + 1)), dim3(64), 0, s, P, sc, 1); }
     { mi_prof_scope p(ctx, "k_lz2_mid<128>", s, (uint64_t)nb * P.block);
