@@ -286,11 +286,26 @@ mi_status mi_deflate_h_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t 
  * whole bytes, starts on a byte boundary and never refers to an earlier block.  The block type is
  * the shortest in bits of dynamic Huffman (BTYPE 10), fixed Huffman (01) and stored (00), ties in
  * that order, all three sized exactly from the histograms; a stored block of 65 536 bytes is two
- * stored blocks (LEN <= 65 535).  Codes: literal/length and distance lengths <= 15, code-length
- * lengths <= 7, every code complete; a code with fewer than two used symbols is padded to two codes
- * of length 1 as zlib pads it; end-of-block is always coded; the code lengths are run-length coded
- * with 16/17/18.  The stream ends with 03 00 (a final fixed block with only end-of-block); for
- * n = 0 the raw stream is just 03 00.
+ * stored blocks (LEN <= 65 535).  Sizes in bits (end-of-block counted in both Huffman forms):
+ *   dynamic  3 + 14 + 3 HCLEN + code-length symbols with their extra bits + tokens with extra bits
+ *   fixed    3 + tokens with extra bits in the fixed code
+ *   stored   40 ceil(n / 65535) + 8 n
+ * Codes: literal/length and distance lengths <= 15, code-length lengths <= 7, every code complete.
+ * The lengths are the mode-H heap's (leaves in symbol order) over the block's tally, end-of-block
+ * always counted.  A code with fewer than two used symbols gets two codes of length 1 as zlib's
+ * build_tree pads: none used -> symbols 0 and 1; one used, s -> s and s + 1 if s < 2, else s and 0.
+ * Where a length exceeds the limit L (15; 7 for the code-length code): every length above L is
+ * clamped to L; while the Kraft sum exceeds 1, one code moves a level down, from the deepest level
+ * l < L that has one (l >= 1); while it is below 1, one code moves a level up, from the deepest
+ * level l <= L (l >= 2) that has one and whose step 2^-l still fits; the level counts are then dealt
+ * out to the used symbols in (unlimited length, symbol) order, the shortest level first.
+ * Header: HLIT is trimmed while > 257 and the last literal/length length is 0, HDIST while > 1 and
+ * the last distance length is 0, HCLEN while > 4 and the last code-length length in RFC order is 0.
+ * The HLIT + HDIST lengths are run-length coded as ONE sequence: a run of r zeros as 18s of
+ * min(r, 138) while r >= 11, then one 17 if r >= 3; a run of r copies of v != 0 as v, then 16s of
+ * min(rest, 6) while rest >= 3; whatever is left of a run is written as plain lengths.  The stream
+ * ends with 03 00 (a final fixed block with only end-of-block); for n = 0 the raw stream is just
+ * 03 00.  oracle/orc_defz.c restates all of this on the CPU; the encoder gives its bytes.
  * Containers: MI_CONTAINER_RAW the above; MI_CONTAINER_ZLIB 78 9C, the raw stream, Adler-32
  * big-endian; MI_CONTAINER_GZIP 1F 8B 08 00 00 00 00 00 00 FF (no flags, MTIME 0, OS 255: the
  * output is reproducible), the raw stream, CRC-32 little-endian, ISIZE = n mod 2^32 little-endian.

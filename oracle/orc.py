@@ -19,7 +19,7 @@ COVERED32 = 0xFFFFFFFE
 
 def build(force=False):
     so = os.path.join(_HERE, "liborc.so")
-    srcs = [os.path.join(_HERE, f) for f in ("orc_lz.c", "orc_huff.c", "orc_fse.c", "orc_defh.c", "orc_table.h")]
+    srcs = [os.path.join(_HERE, f) for f in ("orc_lz.c", "orc_huff.c", "orc_fse.c", "orc_defh.c", "orc_defz.c", "orc_table.h")]
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["make", "-s", "-C", _HERE, "liborc.so"])
     return so
@@ -83,6 +83,20 @@ def lib():
         L.orc_defh_decode_block.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         L.orc_defh_lengths.restype = None
         L.orc_defh_lengths.argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_defz_lengths.restype = C.c_int
+        L.orc_defz_lengths.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.orc_defz_record_cap.restype = C.c_uint64
+        L.orc_defz_record_cap.argtypes = [C.c_uint32]
+        L.orc_defz_record.restype = C.c_uint64
+        L.orc_defz_record.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_defz_stream_cap.restype = C.c_uint64
+        L.orc_defz_stream_cap.argtypes = [C.c_uint64, C.c_uint32]
+        L.orc_defz_stream.restype = C.c_uint64
+        L.orc_defz_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_crc32.restype = C.c_uint32
+        L.orc_crc32.argtypes = [C.c_void_p, C.c_uint64]
+        L.orc_adler32.restype = C.c_uint32
+        L.orc_adler32.argtypes = [C.c_void_p, C.c_uint64]
         _LIB = L
     return _LIB
 
@@ -337,3 +351,69 @@ def defh_lengths(freq):
     ln = np.zeros(286, dtype=np.uint8)
     lib().orc_defh_lengths(_p(f), _p(ln))
     return ln
+
+
+# ---------------------------------------------------------------- mode Z (standard DEFLATE, oracle/orc_defz.c)
+DEFZ_CONTAINERS = {"raw": 0, "zlib": 1, "gzip": 2}
+DEFZ_INFO = ("type", "dyn_bits", "fix_bits", "sto_bits", "lim_ll", "lim_dc", "lim_cl", "clip", "hlit", "hdist", "hclen")
+
+
+def _bytes_u8(data):
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, dtype=np.uint8)
+    return np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))
+
+
+def defz_lengths(freq, limit):
+    """length-limited code lengths over len(freq) <= 288 symbols (heap, zlib's padding, limiter) -> (u8 lengths, limiter fired)"""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    ln = np.zeros(max(len(f), 2), dtype=np.uint8)
+    fired = lib().orc_defz_lengths(_p(f), len(f), limit, _p(ln))
+    return ln[: len(f)], bool(fired)
+
+
+def defz_record(tokens, block_data, force=None):
+    """the mode-Z record of one block: its byte tokens (orc.Deflate / deflate_stream) and its input bytes -> (record bytes,
+    info dict: type, the three sizes in bits, the three limiter flags, clip, hlit, hdist, hclen).  force 0 / 1 / 2 writes
+    that block type whatever it costs."""
+    t = np.ascontiguousarray(tokens, dtype=np.uint8)
+    src = _bytes_u8(block_data)
+    n = len(src)
+    if n < 1 or n > 65536:
+        raise ValueError("a block holds 1..65536 bytes")
+    L = lib()
+    out = np.zeros(L.orc_defz_record_cap(n), dtype=np.uint8)
+    info = np.zeros(len(DEFZ_INFO), dtype=np.uint64)
+    m = L.orc_defz_record(_p(t), len(t), _p(src), n, -1 if force is None else int(force), _p(out), _p(info))
+    if m == 0:
+        raise MemoryError
+    return out[:m].tobytes(), {k: int(v) for k, v in zip(DEFZ_INFO, info)}
+
+
+def defz_stream(data, block=65536, container="gzip", tokens=None):
+    """the whole mode-Z stream -> (bytes, block table: list of nblocks + 1 bit offsets).  tokens: (token bytes, per-block
+    sizes) of deflate_stream(data, block) if already at hand."""
+    src = _bytes_u8(data)
+    n = len(src)
+    tok, sizes = tokens if tokens is not None else deflate_stream(src, block, True)
+    tok = np.ascontiguousarray(tok, dtype=np.uint8)
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    nb = (n + block - 1) // block
+    L = lib()
+    out = np.zeros(L.orc_defz_stream_cap(n, block), dtype=np.uint8)
+    bits = np.zeros(nb + 1, dtype=np.uint64)
+    c = DEFZ_CONTAINERS.get(container, container)
+    m = L.orc_defz_stream(_p(src), n, block, c, _p(tok), _p(sizes), _p(out), _p(bits))
+    if m == 0:
+        raise ValueError("orc_defz_stream failed")
+    return out[:m].tobytes(), [int(v) for v in bits]
+
+
+def crc32(data):
+    src = _bytes_u8(data)
+    return int(lib().orc_crc32(_p(src), len(src)))
+
+
+def adler32(data):
+    src = _bytes_u8(data)
+    return int(lib().orc_adler32(_p(src), len(src)))

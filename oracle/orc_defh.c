@@ -29,8 +29,10 @@
 
 #define DEFH_NSYM 286
 
-typedef struct { uint32_t freq[2 * DEFH_NSYM]; int16_t left[2 * DEFH_NSYM], right[2 * DEFH_NSYM]; int n; } defh_tree;
-typedef struct { int16_t a[DEFH_NSYM]; int n; } defh_heap;
+#define HEAP_NSYM 288                                      /* the largest alphabet (mode Z's literal/length) */
+
+typedef struct { uint32_t freq[2 * HEAP_NSYM]; int16_t left[2 * HEAP_NSYM], right[2 * HEAP_NSYM]; int n; } defh_tree;
+typedef struct { int16_t a[HEAP_NSYM]; int n; } defh_heap;
 
 static void dh_up(defh_heap *h, const defh_tree *t, int i)
 {
@@ -60,22 +62,24 @@ static int dh_pop(defh_heap *h, const defh_tree *t)
     return id;
 }
 
-/* code lengths from the reference heap procedure (leaves enqueued in symbol order) */
-void orc_defh_lengths(const uint32_t freq[DEFH_NSYM], uint8_t len[DEFH_NSYM])
+/* unlimited code lengths over freq[0, nsym) (nsym <= 288) from the reference heap procedure (leaves enqueued in symbol
+ * order).  Returns the number of used symbols; with exactly one, its length is 1 (mode H's rule: mode Z pads instead). */
+int orc_heap_lengths(const uint32_t *freq, int nsym, uint8_t *len)
 {
-    defh_tree t; defh_heap h; int leaf_of[DEFH_NSYM];
+    defh_tree t; defh_heap h; int leaf_of[HEAP_NSYM];
     t.n = 0; h.n = 0;
-    memset(len, 0, DEFH_NSYM);
-    for (int s = 0; s < DEFH_NSYM; ++s) {
+    memset(len, 0, (size_t)nsym);
+    for (int s = 0; s < nsym; ++s) {
         leaf_of[s] = -1;
         if (!freq[s]) continue;
         int id = t.n++;
         t.freq[id] = freq[s]; t.left[id] = t.right[id] = -1; leaf_of[s] = id;
         h.a[h.n++] = (int16_t)id; dh_up(&h, &t, h.n - 1);
     }
-    if (t.n == 0) return;
-    if (t.n == 1) { for (int s = 0; s < DEFH_NSYM; ++s) if (freq[s]) len[s] = 1; return; }
-    int parent[2 * DEFH_NSYM];
+    const int used = t.n;
+    if (used == 0) return 0;
+    if (used == 1) { for (int s = 0; s < nsym; ++s) if (freq[s]) len[s] = 1; return 1; }
+    int parent[2 * HEAP_NSYM];
     while (h.n > 1) {
         int l = dh_pop(&h, &t), r = dh_pop(&h, &t), id = t.n++;
         t.freq[id] = t.freq[l] + t.freq[r]; t.left[id] = (int16_t)l; t.right[id] = (int16_t)r;
@@ -83,12 +87,19 @@ void orc_defh_lengths(const uint32_t freq[DEFH_NSYM], uint8_t len[DEFH_NSYM])
         h.a[h.n++] = (int16_t)id; dh_up(&h, &t, h.n - 1);
     }
     int root = dh_pop(&h, &t);
-    for (int s = 0; s < DEFH_NSYM; ++s) {
+    for (int s = 0; s < nsym; ++s) {
         if (leaf_of[s] < 0) continue;
         int d = 0, node = leaf_of[s];
         while (node != root) { node = parent[node]; ++d; }
         len[s] = (uint8_t)d;
     }
+    return used;
+}
+
+/* code lengths from the reference heap procedure (leaves enqueued in symbol order) */
+void orc_defh_lengths(const uint32_t freq[DEFH_NSYM], uint8_t len[DEFH_NSYM])
+{
+    orc_heap_lengths(freq, DEFH_NSYM, len);
 }
 
 /* canonical codes: by (length, symbol) */
