@@ -58,6 +58,7 @@ EXPORTS = [
     "mi_lz77_old_bound_bytes", "mi_lz77_old_encode_dev", "mi_lz77_old_encode", "mi_lz77_whole_decode_dev", "mi_lz77_whole_decode",
     "mi_deflate_h_bound_bytes", "mi_deflate_h_encode_dev", "mi_deflate_h_decode_dev", "mi_deflate_h_encode", "mi_deflate_h_decode",
     "mi_deflate_z_bound_bytes", "mi_deflate_z_encode_dev", "mi_deflate_z_encode", "mi_crc32_dev", "mi_adler32_dev",
+    "mi_inflate_dev", "mi_inflate",
     "mi_fse_block_bound", "mi_fse_encode_dev", "mi_fse_decode_dev", "mi_fse_encode", "mi_fse_decode", "mi_fse_normalise_dev",
     "mi_set_profiling", "mi_get_kernel_times",
     "mi_multi_create", "mi_multi_destroy", "mi_multi_ndev", "mi_multi_ctx", "mi_multi_transport", "mi_multi_last_transport_error",
@@ -139,6 +140,10 @@ def lib():
             L.mi_deflate_z_encode.argtypes = [vp, C.POINTER(LzParams), u32, vp, u64, vp, u64, vp, vp]
             L.mi_crc32_dev.argtypes = [vp, vp, u64, vp, vp]
             L.mi_adler32_dev.argtypes = [vp, vp, u64, vp, vp]
+        if hasattr(L, "mi_inflate_dev"):
+            u32 = C.c_uint32
+            L.mi_inflate_dev.argtypes = [vp, u32, u32, vp, u64, vp, vp, u64, u32, vp]
+            L.mi_inflate.argtypes = [vp, u32, u32, vp, u64, vp, vp, u64, u32]
         if hasattr(L, "mi_fse_encode_dev"):
             L.mi_fse_block_bound.restype = u64
             L.mi_fse_block_bound.argtypes = [C.POINTER(FseParams)]

@@ -272,3 +272,108 @@ def crc32(data, ctx=None):
 def adler32(data, ctx=None):
     """Adler-32 of the buffer on the GPU (the value zlib.adler32 gives)"""
     return _checksum("mi_adler32_dev", data, ctx)
+
+
+# ---- inflate: standard DEFLATE read back on the GPU from a table of restart points (include/mi_codec.h) -----------
+MI_INFLATE_NO_CHECKSUM = 1
+
+
+def _inflate_dev(ctx, c, block, d_stream, stream_bytes, d_bits, n, verify):
+    out = torch.empty(max(n, 1), dtype=torch.uint8, device=ctx.device)
+    st = ctx.L.mi_inflate_dev(ctx.h, c, block, C.c_void_p(d_stream.data_ptr()), stream_bytes, C.c_void_p(d_bits.data_ptr()),
+                              C.c_void_p(out.data_ptr()), n, 0 if verify else MI_INFLATE_NO_CHECKSUM, ctx.stream_ptr())
+    _lib.check(st, "mi_inflate_dev")
+    return out[:n]
+
+
+def decompress_z(stream, ctx=None, verify=True):
+    """Inflate a ZStream on the GPU, one wave per record -> uint8 device tensor of stream.n bytes.  verify=False skips the
+    comparison of the container's Adler-32 / CRC-32 with that of the decoded bytes."""
+    ctx = ctx or default_context()
+    return _inflate_dev(ctx, stream.container, stream.p.block, stream.data, stream.nbytes, stream.block_bits, stream.n, verify)
+
+
+def gzip_header_bytes(buf):
+    """length of the RFC 1952 member header at the start of `buf`"""
+    if len(buf) < 10 or buf[0] != 0x1F or buf[1] != 0x8B:
+        raise ValueError("not a gzip stream")
+    flg, pos = buf[3], 10
+    if flg & 4:
+        pos += 2 + (buf[pos] | (buf[pos + 1] << 8))
+    for f in (8, 16):
+        if flg & f:
+            pos = bytes(buf).index(b"\0", pos) + 1
+    if flg & 2:
+        pos += 2
+    return pos
+
+
+def inflate(data, n, seg_bits=None, block=None, container="gzip", ctx=None, verify=True):
+    """Inflate standard DEFLATE from anywhere (bytes or a tensor) -> uint8 device tensor of n bytes.
+
+    With seg_bits (list, array or tensor of ceil(n / block) + 1 bit offsets: the start of every segment, then the start of
+    the closing part) and block: one wave per segment.  With seg_bits=None the stream is ONE segment (one wave: correct,
+    slow): the wrapper finds the end of the container header, and takes the end of the DEFLATE data to be the stream's end
+    without its trailer — less a closing 03 00 if the stream ends in one (mode Z, zlib's Z_FINISH after a flush); otherwise
+    the last block of the stream must be the data block itself (zlib.compress).  Anything else needs a table."""
+    ctx = ctx or default_context()
+    c = CONTAINERS.get(container, container)
+    d_stream = as_device_bytes(data, ctx.device)
+    nbytes = d_stream.numel()
+    if nbytes == 0:
+        raise ValueError("an empty stream (the shortest DEFLATE stream is 03 00)")
+    if seg_bits is None:
+        if c not in CONTAINERS.values():
+            raise ValueError(container)
+        block = max(n, 1)
+        head = bytes(d_stream[: min(nbytes, 65536 + 2048)].cpu().numpy().tobytes()) if c == 2 else b""
+        start = gzip_header_bytes(head) if c == 2 else (2 if c == 1 else 0)
+        end = nbytes - (8 if c == 2 else 4 if c == 1 else 0)
+        if end < start:
+            raise ValueError("the stream is shorter than its container")
+        if n == 0:
+            table = [8 * start]
+        else:
+            tail = bytes(d_stream[max(end - 2, start): end].cpu().numpy().tobytes())
+            # 03 00 at the end is a closing block only if the data before it stops at a byte boundary, which cannot be told
+            # without decoding: both readings are legal streams, so the closing-block reading is tried first
+            tables = ([[8 * start, 8 * (end - 2)]] if tail == b"\x03\x00" else []) + [[8 * start, 8 * end]]
+            last = None
+            for t in tables:
+                bits = torch.tensor(t, dtype=torch.int64, device=ctx.device)
+                try:
+                    return _inflate_dev(ctx, c, block, d_stream, nbytes, bits, n, verify)
+                except _lib.MiError as e:
+                    if e.status != 8:
+                        raise
+                    last = e
+            raise ValueError("the stream does not inflate as one segment (corrupt, or its closing part is neither 03 00 nor "
+                             "empty): pass seg_bits and block") from last
+        bits = torch.tensor(table, dtype=torch.int64, device=ctx.device)
+        return _inflate_dev(ctx, c, block, d_stream, nbytes, bits, n, verify)
+    if not block:
+        raise ValueError("seg_bits needs block")
+    nseg = (n + block - 1) // block
+    if torch.is_tensor(seg_bits):
+        bits = seg_bits.to(device=ctx.device, dtype=torch.int64).contiguous()
+    else:
+        bits = torch.from_numpy(np.asarray(seg_bits, dtype=np.uint64).astype(np.int64)).to(ctx.device)
+    if bits.numel() != nseg + 1:
+        raise ValueError(f"seg_bits has {bits.numel()} entries, ceil(n / block) + 1 = {nseg + 1} expected")
+    return _inflate_dev(ctx, c, block, d_stream, nbytes, bits, n, verify)
+
+
+def decompress_z_host(data, table, n, block, container="gzip", ctx=None, verify=True):
+    """the host-buffer entry point (mi_inflate), the twin of compress_z_host -> bytes"""
+    ctx = ctx or default_context()
+    c = CONTAINERS.get(container, container)
+    buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+    bits = np.ascontiguousarray(np.asarray(table, dtype=np.uint64))
+    nseg = (n + block - 1) // block if block else 0
+    if bits.size != nseg + 1:
+        raise ValueError(f"the table has {bits.size} entries, ceil(n / block) + 1 = {nseg + 1} expected")
+    out = np.zeros(max(n, 1), dtype=np.uint8)
+    st = ctx.L.mi_inflate(ctx.h, c, block, buf.ctypes.data_as(C.c_void_p), buf.size, bits.ctypes.data_as(C.c_void_p),
+                          out.ctypes.data_as(C.c_void_p), n, 0 if verify else MI_INFLATE_NO_CHECKSUM)
+    _lib.check(st, "mi_inflate")
+    return out[:n].tobytes()

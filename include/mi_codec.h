@@ -336,6 +336,61 @@ mi_status mi_crc32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d
 mi_status mi_adler32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_adler, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Inflate: standard DEFLATE read back on the GPU from a table of restart points — a mode-Z
+ * stream with the table its encoder wrote, or any stream cut the same way (stock zlib with
+ * Z_FULL_FLUSH every `block` input bytes: INTEGRATION.md has the recipe).
+ *
+ * d_seg_bits u64[nseg+1], nseg = ceil(n / block): entry s is the bit offset in d_stream where
+ * SEGMENT s starts (entry 0 = the end of the container header: 0 for raw, 16 for zlib, 8 * the
+ * header length for gzip), entry nseg where the closing part starts; all multiples of 8.  It is
+ * exactly the d_block_bits of mi_deflate_z_encode_dev, so a mode-Z stream decodes with the
+ * arguments it was encoded with.  `block` is a plain number, 1 .. 2^31 - 1 (positions inside a
+ * segment are 32-bit); n = 0 is legal (no segment: only the frame is checked).
+ * Segment s: whole DEFLATE blocks with BFINAL = 0, of any type (stored, fixed, dynamic; the full
+ * RFC 1951 alphabet: lengths to 258, distances to 32 768, codes to 15 bits), that use the bits
+ * [entry s, entry s+1) exactly and inflate to exactly the bytes [s * block, min((s+1) * block, n))
+ * without referring to anything before them.  One wave decodes it.
+ * Closing part, from entry nseg: blocks that produce no bytes (stored with LEN = 0, or fixed with
+ * end-of-block alone; an empty dynamic block is not accepted there), the last with BFINAL = 1 —
+ * mode Z and zlib write 03 00 — then at the next byte boundary the trailer: none (raw), Adler-32
+ * big-endian (zlib), CRC-32 and ISIZE = n mod 2^32 little-endian (gzip); the stream ends exactly
+ * there (stream_bytes).
+ * One relaxation: in a one-segment call (nseg == 1) the BFINAL = 1 block may be the segment's
+ * last block; entry 1 is then the end of the DEFLATE data (the byte after its last bit) and the
+ * closing part is empty.  zlib.compress(x) writes that.  A stream without a table is one segment
+ * (block >= n): correct, and slow — one wave.
+ * Header: raw none; zlib CM = 8, CINFO <= 7, (CMF * 256 + FLG) % 31 == 0, FDICT = 0; gzip 1F 8B,
+ * CM = 8, reserved flag bits zero, FEXTRA / FNAME / FCOMMENT / FHCRC skipped by their lengths
+ * (FHCRC not verified).
+ * MI_ERR_CORRUPT: a table entry that is not a multiple of 8, decreasing or past the stream; a
+ * segment that uses more or fewer bits than it has or produces more or fewer bytes than its range;
+ * BTYPE 11; a stored block whose NLEN is not ~LEN; HLIT > 286 or HDIST > 30; an over-subscribed
+ * code; an incomplete code (except a distance code with a single code of length 1, or with no
+ * code at all in a block of literals); no end-of-block code; a repeat (16) with no previous
+ * length or a run past HLIT + HDIST; symbols 286, 287, distance codes 30, 31; a distance reaching
+ * before the segment's first byte; BFINAL = 1 inside a segment (but see above); a header, closing
+ * part or trailer other than described; ISIZE != n mod 2^32; a checksum that differs from that of
+ * the decoded bytes (mi_crc32_dev / mi_adler32_dev run after the inflate kernel and are compared
+ * on the device) unless MI_INFLATE_NO_CHECKSUM is set.
+ * MI_ERR_ARG: NULL pointers, an unknown container, block 0 or above 2^31 - 1, d_stream not 4-byte
+ * aligned, unknown flag bits.
+ * Reads stay inside [d_stream, d_stream + stream_bytes) rounded out to whole aligned 4-byte words
+ * and inside the segment's own bits whatever the (untrusted) table says; writes inside the
+ * segment's own output range; every loop is bounded by the segment's bit or byte count.
+ * mi_inflate_dev synchronises `stream` before returning; it uses the context workspace (8 KiB of
+ * checksum partials): one call of a context in flight at a time.
+ * Out of scope: finding restart points in a stream that comes without a table, multi-member
+ * gzip, preset dictionaries, MI_FRAME_* packing of mode Z, the multi-GPU path.
+ * ------------------------------------------------------------------------------------ */
+#define MI_INFLATE_NO_CHECKSUM 1u   /* skip the Adler-32 / CRC-32 comparison (ISIZE and the frame are still checked) */
+mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t block, const uint8_t *d_stream, uint64_t stream_bytes,
+                         const uint64_t *d_seg_bits, uint8_t *d_out, uint64_t n, uint32_t flags, void *stream);
+/* host buffers: the table is validated (mi_validate_block_table, 8-bit alignment) before anything is copied; copy in,
+ * decode, copy out, in one piece */
+mi_status mi_inflate(mi_ctx *ctx, uint32_t container, uint32_t block, const uint8_t *h_stream, uint64_t stream_bytes,
+                     const uint64_t *h_seg_bits, uint8_t *h_out, uint64_t n, uint32_t flags);
+
+/* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is
  * defined by this build).  Record layout in include/mi_fse.h.
  * ------------------------------------------------------------------------------------ */

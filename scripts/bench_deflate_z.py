@@ -1,5 +1,7 @@
 """Mode Z (standard DEFLATE) against mode H on bench.py's corpus: GB/s and ratio, warm, HIP events, alternating encodes in
-one process; zlib.compress levels 1 and 6 on one host core as the CPU baseline.
+one process; zlib.compress levels 1 and 6 on one host core as the CPU baseline.  Then the decoders, the same way: the GPU
+inflater (mi_inflate_dev) on the raw and gzip streams, with and without its checksum pass, against mode H's decoder, and
+zlib.decompress on one host core.
 
     python scripts/bench_deflate_z.py [--bytes 1000000000] [--repeats 5] [--cpu-bytes 100000000]
 """
@@ -68,7 +70,53 @@ def main():
         med = t[len(t) // 2]
         res[m] = dict(ms_median=round(med, 3), ms_min=round(t[0], 3), gbps=round(n / med / 1e6, 3), ratio=round(n / size[m], 4),
                       bytes_out=size[m])
+    # ---- decoders: every stream in a buffer of its own, the output compared once, then timed alternating
+    streams = {}
+    for m, f in modes:
+        nb = f()()
+        streams[m] = (out[:nb].clone(), bits[: nblocks + 1].clone(), nb)
+    y = torch.empty(n, dtype=torch.uint8, device=dev)
+    yp = C.c_void_p(y.data_ptr())
+
+    def dec_h():
+        d, t, nb = streams["mode_h"]
+        assert ctx.L.mi_deflate_h_decode_dev(ctx.h, C.byref(p), C.c_void_p(d.data_ptr()), nb, C.c_void_p(t.data_ptr()), yp, n, s) == 0
+
+    def dec_z(m, c, flags):
+        def f():
+            d, t, nb = streams[m]
+            assert ctx.L.mi_inflate_dev(ctx.h, c, p.block, C.c_void_p(d.data_ptr()), nb, C.c_void_p(t.data_ptr()), yp, n, flags, s) == 0
+        return f
+
+    decs = [("mode_h_decode", dec_h), ("mode_z_decode_raw", dec_z("mode_z_raw", 0, 0)),
+            ("mode_z_decode_gzip", dec_z("mode_z_gzip", 2, 0)),
+            ("mode_z_decode_gzip_no_checksum", dec_z("mode_z_gzip", 2, lz.MI_INFLATE_NO_CHECKSUM))]
+    for m, f in decs:                                           # warm, and right
+        y.zero_()
+        f()
+        assert torch.equal(y, x), m
+    dtimes = {m: [] for m, _ in decs}
+    for _ in range(a.repeats):
+        for m, f in decs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize()
+            dtimes[m].append(e0.elapsed_time(e1))
+    for m, _ in decs:
+        t = sorted(dtimes[m])
+        med = t[len(t) // 2]
+        res[m] = dict(ms_median=round(med, 3), ms_min=round(t[0], 3), gbps=round(n / med / 1e6, 3))
+    res["mode_z_decode_over_mode_h_decode"] = round(res["mode_z_decode_raw"]["gbps"] / res["mode_h_decode"]["gbps"], 3)
     cpu = x[: a.cpu_bytes].cpu().numpy().tobytes()
+    zc = streams["mode_z_gzip"][0].cpu().numpy().tobytes() if a.cpu_bytes >= n else lz.compress_z(x[: a.cpu_bytes], p, "gzip").tobytes()
+    t0 = time.perf_counter()
+    back = zlib.decompress(zc, 31)
+    dt = time.perf_counter() - t0
+    assert len(back) == len(cpu)
+    res["zlib_decompress_1core"] = dict(bytes_out=len(cpu), gbps=round(len(cpu) / dt / 1e9, 4))
     for lvl in (1, 6):
         t0 = time.perf_counter()
         z = zlib.compress(cpu, lvl)

@@ -3,10 +3,12 @@
     python scripts/fuzz_campaign.py [cases] [first_seed] [wide]
 "wide": every case is the lz77 flavour on blocks of 128 KiB .. 1 MiB (the time-sliced finder, its fallback on runs/pages).
 Every case: a random input family / length / block size / flavour; find() at every position against the oracle's literal
-table, the stream round trip, and for deflate the token stream against the oracle.  Prints one line per failure."""
+table, the stream round trip, and for deflate the token stream against the oracle, the mode-H round trip and the
+mode-Z round trip through the GPU inflater.  Prints one line per failure."""
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -61,6 +63,13 @@ for i in range(cases):
             sth = lz.compress_h(data, p)
             if not np.array_equal(lz.decompress_h(sth).cpu().numpy(), data):
                 raise AssertionError("mode H round trip")
+            # mode Z: encode, inflate on the GPU (with the container's checksum), compare; zlib reads the same stream
+            container = ["raw", "zlib", "gzip"][seed % 3]
+            stz = lz.compress_z(data, p, container)
+            if not np.array_equal(lz.decompress_z(stz).cpu().numpy(), data):
+                raise AssertionError("mode Z round trip")
+            if zlib.decompress(stz.tobytes(), {"raw": -15, "zlib": 15, "gzip": 31}[container]) != data.tobytes():
+                raise AssertionError("mode Z against zlib")
     except Exception as e:
         fails += 1
         print(f"FAIL seed {seed} {kind} n={n} block={block} {flavour} w{wbits}: {e}", flush=True)
