@@ -13,15 +13,18 @@
 //
 // Block record, 4-byte aligned:   u32 n_tokens | u8 len[286] + 2 pad | u32 words[] (MSB-first)
 //
-//   k_defh_encode   one workgroup per block over the token records k_lz_parse_emit left (mode H)
+//   k_defh_lengths  one wave per block: code lengths and canonical codes from the tally k_lz_parse_emit left, and the
+//                   record's SIZE (defh_size.h: it follows from the tally and the lengths alone)
+//   (k_lz_scan_blocks, lz_emit.hip: sizes -> offsets)
+//   k_defh_encode   one workgroup per block over the token records k_lz_parse_emit left: packs the record straight into
+//                   its place in the caller's stream — records are whole dwords, so a record's dwords are its own
 //   k_defh_decode   one wave per block: record -> tokens -> bytes (LZ copy in LDS), no token stream in HBM
 #include "lz_common.h"
 #include "lz_decode.h"
 #include "heap_cells.h"
+#include "defh_size.h"              // DEFH_NSYM, DEFH_HDR, the record's size from tally and lengths
 #include <stdlib.h>
 
-#define DEFH_NSYM     286
-#define DEFH_HDR      292u          // bytes before the packed words
 // 256 threads per block: the kernel spends its time behind ONE lane (the heap), so what counts is how many blocks a CU holds —
 // wave slots, not LDS, are the limit (32 per CU: 8 blocks of 4 waves instead of 4 of 8).  Same box: 512 / 256 / 128 threads
 // 17.30 / 17.72 / 17.68 GB/s for the whole mode-H step.
@@ -80,13 +83,15 @@ __device__ __forceinline__ void defh_canonical(const uint8_t *s_len, uint32_t *s
 
 // Two kernels since round 3.  The code LENGTHS wait ~1.4 M cycles per block behind one lane (the reference heap): that kernel is
 // ONE wave per block with 8 KiB of LDS — twenty blocks in flight per CU where the fused kernel (256 threads, the pack stage's
-// 5.6 KiB window) held eight.  It leaves the lengths in the record's header and the canonical codes behind the tally in the
-// block's slot; the pack kernel reads both.
-#define DEFH_CODE_AT (LZ_DEFH_HIST_AT + 288u)          // slot words [.., +288): the canonical codes, from k_defh_lengths to k_defh_pack
-static_assert(DEFH_CODE_AT + 288u <= LZ_SLOT_WORDS, "tally and codes live behind the record in the slot");
+// 5.6 KiB window) held eight.  It leaves the lengths at the head of the block's slot (where the record's header would be), the
+// canonical codes and the token count behind the tally, and the record's size in block_bits[lb]; the pack kernel reads the
+// first three, the scan between the two kernels turns the sizes into the records' places.
+#define DEFH_CODE_AT (LZ_DEFH_HIST_AT + 288u)          // slot words [.., +288): the canonical codes, from k_defh_lengths to k_defh_encode
+#define DEFH_NTOK_AT (DEFH_CODE_AT + 288u)             // slot word: the block's token count (the tally's sum)
+static_assert(DEFH_NTOK_AT + 1u <= LZ_SLOT_WORDS, "tally, codes and token count live at the end of the slot");
 
 __global__ __launch_bounds__(64)
-void k_defh_lengths(uint32_t *__restrict__ slots)
+void k_defh_lengths(uint32_t *__restrict__ slots, uint64_t *__restrict__ block_bits)
 {
     // 4.5 KiB of LDS (8 before): the tally's array becomes the codes' once the leaves are enqueued, the heap cells carry the
     // frequencies — the wave holds its LDS for the whole serial merge, and LDS-seconds are what the pipeline's stages compete for
@@ -140,13 +145,28 @@ void k_defh_lengths(uint32_t *__restrict__ slots)
         s_len[sy] = (uint8_t)len;
     }
     __syncthreads();
+    // ---- the record's size, while the tally is still there (s_hist becomes s_code below): 286 multiply-adds over the wave
+    {
+        uint32_t ntok;
+        uint32_t bits = defh_payload_bits(s_hist, s_len, (uint32_t)tid, 64u, &ntok);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { bits += __shfl_xor(bits, o); ntok += __shfl_xor(ntok, o); }
+        if (tid == 0) {
+            block_bits[blockIdx.x] = 8ull * defh_record_bytes(bits);      // replaces the token count k_lz_parse_emit left there
+            out[DEFH_NTOK_AT] = ntok;
+        }
+    }
     defh_canonical(s_len, s_code, s_count, s_next);
-    for (int i = tid; i < (DEFH_NSYM + 2) / 4; i += 64) out[1 + i] = reinterpret_cast<const uint32_t *>(s_len)[i];     // the record's header
+    for (int i = tid; i < (DEFH_NSYM + 2) / 4; i += 64) out[1 + i] = reinterpret_cast<const uint32_t *>(s_len)[i];     // the header's lengths
     for (int i = tid; i < DEFH_NSYM + 2; i += 64) out[DEFH_CODE_AT + i] = s_code[i];
 }
 
+// The record goes straight to its final place: word (base + excl_local[lb]) / 32 of the caller's stream (base: the bits of the
+// batches before this one; both multiples of 32).  Every store is held below cap_words — never past the caller's buffer (the
+// host checked the capacity against the bound) — and nothing is written past the record's own last word.
 __global__ __launch_bounds__(DEFH_THREADS)
-void k_defh_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, uint64_t *__restrict__ block_bits)
+void k_defh_encode(const uint32_t *__restrict__ trec_all, const uint32_t *__restrict__ slots, const uint64_t *__restrict__ excl_local,
+                   const uint64_t *__restrict__ base_bits, uint32_t *__restrict__ d_out, uint64_t cap_words)
 {
     __shared__ uint32_t s_code[DEFH_NSYM + 2];
     __shared__ __attribute__((aligned(16))) uint8_t s_len[DEFH_NSYM + 2];
@@ -155,19 +175,24 @@ void k_defh_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
 
     const int tid = threadIdx.x;
     const uint32_t lb = blockIdx.x;
-    const uint32_t ntok = (uint32_t)block_bits[lb];                   // k_lz_parse_emit (mode H) left the token count here
     const uint32_t *trec = trec_all + (size_t)lb * LZ_MAX_BLOCK;
-    uint32_t *out = slots + (size_t)lb * LZ_SLOT_WORDS;
+    const uint32_t *slot = slots + (size_t)lb * LZ_SLOT_WORDS;
+    const uint32_t ntok = slot[DEFH_NTOK_AT];                         // k_defh_lengths: the tally's sum
+    const uint64_t w_rec = (*base_bits + excl_local[lb]) >> 5;        // the record's first word in the stream
+    uint32_t *out = d_out + w_rec;
+    const uint64_t lim = cap_words > w_rec ? cap_words - w_rec : 0;   // record words [0, lim) are inside the buffer
     auto symbol_of = [](uint32_t r) -> uint32_t { return (r >> 31) ? 256u + clz16(r) : (r & 0xFFu); };
 
-    // ---- lengths and codes: k_defh_lengths left them in the header and behind the tally
-    for (int i = tid; i < DEFH_NSYM + 2; i += DEFH_THREADS) s_code[i] = out[DEFH_CODE_AT + i];
-    for (int i = tid; i < (DEFH_NSYM + 2) / 4; i += DEFH_THREADS) reinterpret_cast<uint32_t *>(s_len)[i] = out[1 + i];
+    // ---- lengths and codes: k_defh_lengths left them at the head of the slot and behind the tally
+    for (int i = tid; i < DEFH_NSYM + 2; i += DEFH_THREADS) s_code[i] = slot[DEFH_CODE_AT + i];
+    for (int i = tid; i < (DEFH_NSYM + 2) / 4; i += DEFH_THREADS) reinterpret_cast<uint32_t *>(s_len)[i] = slot[1 + i];
     __syncthreads();
 
-    // ---- header
-    if (tid == 0) out[0] = ntok;
+    // ---- header: token count, the 286 lengths and two zero pad bytes
+    if (tid == 0 && lim > 0) out[0] = ntok;
+    for (uint32_t i = tid; i < (DEFH_NSYM + 2) / 4; i += DEFH_THREADS) if (1u + i < lim) out[1u + i] = reinterpret_cast<const uint32_t *>(s_len)[i];
     uint32_t *words = out + DEFH_HDR / 4;
+    const uint64_t wlim = lim > DEFH_HDR / 4 ? lim - DEFH_HDR / 4 : 0;   // payload words [0, wlim) are inside the buffer
 
     // ---- pack, DEFH_THREADS * DEFH_PER tokens per round; a thread owns DEFH_PER consecutive tokens
     uint64_t qbase = 0;
@@ -215,21 +240,25 @@ void k_defh_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
         for (int k = 0; k < 4; ++k) { put(c_v[k], c_k[k]); put(x_v[k], x_k[k]); }
         __syncthreads();
         const uint32_t ncomplete = (sh0 + total) >> 5;
-        for (uint32_t i = tid; i < ncomplete; i += DEFH_THREADS) words[w0 + i] = s_stage[i];
+        for (uint32_t i = tid; i < ncomplete; i += DEFH_THREADS) if (w0 + i < wlim) words[w0 + i] = s_stage[i];
         carry = s_stage[ncomplete];
         qbase += total;
         __syncthreads();
     }
-    if (tid == 0) {
-        if (qbase & 31u) words[qbase >> 5] = carry;
-        block_bits[lb] = ((uint64_t)DEFH_HDR + ((qbase + 31) >> 5) * 4) * 8;
-    }
+    if (tid == 0 && (qbase & 31u) && (qbase >> 5) < wlim) words[qbase >> 5] = carry;
 }
 
-void defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, hipStream_t s)
+// The entropy stage of one batch, on one stream: lengths (+ sizes into block_bits), the scan that turns block_bits into offsets
+// in place and publishes the block table (lz_emit.hip), then the pack into the caller's stream at *base_bits + offset.
+void lz_launch_scan_blocks(uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits, uint64_t *excl_global, hipStream_t s);
+
+void defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits,
+                        uint64_t *excl_global, uint8_t *d_out, uint64_t cap_bytes, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_defh_lengths, dim3(nb), dim3(64), 0, s, slots);
-    hipLaunchKernelGGL(k_defh_encode, dim3(nb), dim3(DEFH_THREADS), 0, s, trec, slots, block_bits);
+    hipLaunchKernelGGL(k_defh_lengths, dim3(nb), dim3(64), 0, s, slots, block_bits);
+    lz_launch_scan_blocks(block_bits, nb, base_bits, excl_global, s);
+    hipLaunchKernelGGL(k_defh_encode, dim3(nb), dim3(DEFH_THREADS), 0, s, trec, slots, block_bits, base_bits,
+                       reinterpret_cast<uint32_t *>(d_out), cap_bytes / 4);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -9,8 +9,11 @@
 //                    bit-packed LSB first through an LDS window (lz77.c:144-174: bit i of the
 //                    stream is bit i%8 of byte i/8; deflate byte tokens lz77.c:176-197 are the
 //                    same thing with 16/32-bit tokens)
+//   k_lz_scan_blocks per-block sizes -> offsets in the batch, and the caller's block table
 //   k_lz_concat      block streams -> one stream, bit-contiguous (a funnel-shift gather, one
-//                    thread per output dword)
+//                    thread per output dword).  Not in mode H: its record sizes are known before
+//                    the records are packed (defh_size.h), so the scan runs first and k_defh_encode
+//                    writes every record where it belongs (defh.hip).
 //   (decoders: lz_decode.hip)
 #include "lz_common.h"
 #include "lz2.h"
@@ -451,6 +454,12 @@ void k_lz_scan_blocks(const uint64_t *bits, uint32_t nb, const uint64_t *__restr
 
 __global__ void k_lz_advance(uint64_t *base_bits, const uint64_t *excl_local, uint32_t nb) { *base_bits += excl_local[nb]; }
 
+// (for defh.hip, whose entropy stage runs the scan between its two kernels: in place over the batch's sizes)
+void lz_launch_scan_blocks(uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits, uint64_t *excl_global, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, s, block_bits, nb, base_bits, block_bits, excl_global);
+}
+
 __device__ __forceinline__ uint32_t extract_bits(const uint32_t *w, uint64_t lo, uint32_t k)   // k in 1..32
 {
     const uint64_t wi = lo >> 5; const uint32_t sh = (uint32_t)(lo & 31u);
@@ -525,7 +534,8 @@ mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t
                         const LzScratch &sc, hipStream_t s);
 uint32_t lz_batch_blocks(mi_ctx *ctx, uint64_t nblocks);
 
-void defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, hipStream_t s);
+void defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits,
+                        uint64_t *excl_global, uint8_t *d_out, uint64_t cap_bytes, hipStream_t s);
 // defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
 void defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
                         uint32_t block, uint64_t b0, uint32_t nb, hipStream_t s);
@@ -550,9 +560,11 @@ extern "C" uint64_t mi_deflate_h_bound_bytes(uint64_t n, const mi_lz_params *p);
 mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_in, uint64_t n,
                                    uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, bool *done);
 
-// mode_h = 0: the reference's token stream.  mode_h = 1: the same tokens, entropy coded per block (defh.hip); the
-// per-block records are word aligned, so the same scan / concatenate kernels place them.  mode_h = 2 (z != nullptr): the
-// same tokens as standard DEFLATE records (defz.hip), byte aligned, placed behind the container header; the caller has
+// mode_h = 0: the reference's token stream, packed per block into the block's slot, placed by the scan / concatenate
+// kernels.  mode_h = 1: the same tokens, entropy coded per block (defh.hip); a record's size follows from its tally and code
+// lengths and records are whole dwords, so the scan runs BEFORE the pack and the pack writes every record where it belongs:
+// no slot, no k_lz_concat, the compressed bytes cross HBM once.  mode_h = 2 (z != nullptr): the same tokens as standard
+// DEFLATE records (defz.hip), byte aligned, through slot / scan / concatenate behind the container header; the caller has
 // checked the parameters and the capacity.
 static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
                                 uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, int mode_h,
@@ -620,7 +632,8 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
     } else MI_HIP(ctx, hipMemsetAsync(base_bits, 0, 8, s));
     if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return MI_OK; }
     hipStream_t sb = overlap ? ctx->side : s, sp = overlap ? ctx->parse : s;
-    // stage C of one batch (set k): parse / emit (+ the entropy stage in mode H) / scan / concatenate
+    // stage C of one batch (set k): parse / emit, then scan / concatenate (mode T; mode Z behind its entropy stage) or
+    // mode H's entropy stage with the scan inside it, then the base moves on
     auto stage_c = [&](int k, uint64_t b0, uint32_t nb) -> mi_status {
         uint64_t *excl_local = sc[k].block_bits;                   // reused in place by the scan
         uint32_t *trec = mode_h ? trec_base + (size_t)k * nbmax * LZ_MAX_BLOCK : nullptr;
@@ -630,13 +643,13 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
         }
         if (mode_h == 1) {
             mi_prof_scope ph(ctx, "k_defh_encode", sp, (uint64_t)nb * P.block);
-            defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, sp);
+            defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, base_bits, d_block_bits + b0, d_out, cap_bytes, sp);
         } else if (mode_h == 2) {
             mi_prof_scope ph(ctx, "k_defz_encode", sp, (uint64_t)nb * P.block);
             defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp);
         }
-        hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, sp, sc[k].block_bits, nb, base_bits, excl_local, d_block_bits + b0);
-        {
+        if (mode_h != 1) {
+            hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, sp, sc[k].block_bits, nb, base_bits, excl_local, d_block_bits + b0);
             mi_prof_scope pr(ctx, "k_lz_concat", sp, (uint64_t)nb * P.block);
             const uint64_t typw = (uint64_t)nb * (P.block / 4 + 64);   // about one output byte per input byte; the kernel strides
             hipLaunchKernelGGL(k_lz_concat, dim3((unsigned)((typw + 255) / 256)), dim3(256), 0, sp, sc[k].slot, excl_local, nb,
