@@ -6,7 +6,8 @@
 // (deflate/huffman.h:6 NUM_CODES; huffman.c:49-62: literal b -> b, match with offset d ->
 // 256 + clz16(d)), the per-block tally (lz77.c:206,231,273), MSB-first u32 packing
 // (deflate/huffman.c:16-46) and the heap merge procedure with its tie-breaking
-// (algorithms/huffman/huffman.c:100-163,189-211).  Defined by this project (the bit
+// (algorithms/huffman/huffman.c:100-163,189-211; huff_enc.h holds it, with the canonical-code core and the pack round, for this
+// file and defz.hip).  Defined by this project (the bit
 // stream is PARITY UNPINNED — the reference has no such encoder; the oracle restatement is
 // oracle/orc_defh.c): lengths from that heap, canonical codes by (length, symbol), a match symbol is
 // followed by the offset bits below its leading one and the 5-bit length.
@@ -21,7 +22,8 @@
 //   k_defh_decode   one wave per block: record -> tokens -> bytes (LZ copy in LDS), no token stream in HBM
 #include "lz_common.h"
 #include "lz_decode.h"
-#include "heap_cells.h"
+#include "huff_enc.h"               // the heap merge, canonical codes and the pack round, shared with defz.hip
+#include "internal.h"
 #include "defh_size.h"              // DEFH_NSYM, DEFH_HDR, the record's size from tally and lengths
 #include <stdlib.h>
 
@@ -31,7 +33,6 @@
 #ifndef DEFH_THREADS
 #define DEFH_THREADS  256
 #endif
-#define DEFH_PER      4             // tokens per thread per round
 #define DEFH_MAXBITS  44u           // code <= 24 (65536 tokens: Fibonacci bound) + 15 offset bits + 5 length bits
 // direct LUT of the decoder: 9 bits = 1 KiB of LDS (more waves per CU beat fewer slow-path symbols: 11 / 10 / 9 / 8 / 7 bits
 // decode 17.8 / 19.2 / 19.5 / 18.6 / 18.6 GB/s); decode-side only, the format does not depend on it
@@ -39,46 +40,12 @@
 #define DEFH_LUT_BITS 9
 #endif
 
-// The reference's array heap (algorithms/huffman/huffman.c:100-163: strict '<' on the frequency in both sifts, leaves
-// enqueued in symbol order, first pop = left).  A heap cell holds frequency << 10 | node id (frequencies are <= 65 536
-// tokens, ids < 572), so a comparison is ONE LDS read per node instead of two dependent ones (heap[i], then freq[heap[i]]) and
-// a merged node's frequency comes out of the two cells it pops: no frequency array.  The merge loop runs on one lane and is the
-// critical path of the entropy stage; its sifts read ahead of their decisions (heap_cells.h).  Ties are still decided by
-// position alone: only the frequency field is compared.
-struct DefhHeap {
-    int16_t  parent[2 * DEFH_NSYM];
-    uint32_t heap[DEFH_NSYM + 2];        // frequency << 10 | node id
-    int16_t  leaf_of[DEFH_NSYM];
-    int      nnodes, root;
-};
-typedef HeapCells<uint32_t, 10> DefhCells;
-#define DH_F(c) ((c) >> 10)
-#define DH_ID(c) ((int)((c) & 1023u))
-
 __device__ __forceinline__ uint32_t clz16(uint32_t d) { return (uint32_t)__builtin_clz(d & 0xFFFFu) - 16u; }   // d in 1..65535
 
-// canonical codes from lengths: code[s] = first code of its length + rank among equal lengths (symbol order)
+// canonical codes, MSB first: lengths 1..32 get one, anything longer is counted in bin 33 and gets code 0
 __device__ __forceinline__ void defh_canonical(const uint8_t *s_len, uint32_t *s_code, uint32_t *s_count /*[34]*/, uint32_t *s_next /*[34]*/)
 {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    for (int i = tid; i < 34; i += nt) s_count[i] = 0;
-    __syncthreads();
-    for (int s = tid; s < DEFH_NSYM; s += nt) if (s_len[s]) atomicAdd(&s_count[s_len[s] > 33 ? 33 : s_len[s]], 1u);
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t c = 0;
-        s_next[0] = 0;
-        for (int l = 1; l <= 32; ++l) { c = (c + s_count[l - 1]) << 1; s_next[l] = c; }
-        s_next[33] = 0;
-    }
-    __syncthreads();
-    for (int s = tid; s < DEFH_NSYM; s += nt) {
-        const uint32_t l = s_len[s];
-        uint32_t rank = 0;
-        for (int k = 0; k < s; ++k) rank += (s_len[k] == l);
-        s_code[s] = (l && l <= 32) ? s_next[l] + rank : 0u;
-    }
-    __syncthreads();
+    huff_canonical<32, 34>(s_len, DEFH_NSYM, s_count, s_next, [&](int s, uint32_t, uint32_t code) { s_code[s] = code; });
 }
 
 // Two kernels since round 3.  The code LENGTHS wait ~1.4 M cycles per block behind one lane (the reference heap): that kernel is
@@ -95,7 +62,7 @@ void k_defh_lengths(uint32_t *__restrict__ slots, uint64_t *__restrict__ block_b
 {
     // 4.5 KiB of LDS (8 before): the tally's array becomes the codes' once the leaves are enqueued, the heap cells carry the
     // frequencies — the wave holds its LDS for the whole serial merge, and LDS-seconds are what the pipeline's stages compete for
-    __shared__ DefhHeap h;
+    __shared__ HuffHeap<DEFH_NSYM> h;
     __shared__ uint32_t s_hist[DEFH_NSYM + 2];
     __shared__ __attribute__((aligned(16))) uint8_t s_len[DEFH_NSYM + 2];
     __shared__ uint32_t s_count[34], s_next[34];
@@ -106,44 +73,10 @@ void k_defh_lengths(uint32_t *__restrict__ slots, uint64_t *__restrict__ block_b
     for (int i = tid; i < DEFH_NSYM + 2; i += 64) { s_hist[i] = out[LZ_DEFH_HIST_AT + i]; s_len[i] = 0; }
     for (int i = tid; i < DEFH_NSYM; i += 64) h.leaf_of[i] = -1;
     __syncthreads();
-    // ---- code lengths: the reference heap, leaves enqueued in symbol order (one lane; <= 285 merges)
-    if (tid == 0) {
-        int nheap = 0, nnodes = 0, root = -1;
-        for (int s0 = 0; s0 < DEFH_NSYM; s0 += 8) {
-            uint32_t f8[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) f8[k] = s_hist[s0 + k < DEFH_NSYM ? s0 + k : 0];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int s = s0 + k;
-                const uint32_t f = f8[k];
-                if (s >= DEFH_NSYM || !f) continue;
-                const int id = nnodes++;
-                h.parent[id] = -1; h.leaf_of[s] = (int16_t)id;
-                DefhCells::push(h.heap, nheap, (f << 10) | (uint32_t)id);
-            }
-        }
-        if (nnodes > 1) {
-            while (nheap > 1) {
-                const uint32_t lc = DefhCells::pop(h.heap, nheap), rc = DefhCells::pop(h.heap, nheap);
-                const int id = nnodes++;
-                h.parent[id] = -1;
-                h.parent[DH_ID(lc)] = (int16_t)id; h.parent[DH_ID(rc)] = (int16_t)id;
-                DefhCells::push(h.heap, nheap, ((DH_F(lc) + DH_F(rc)) << 10) | (uint32_t)id);
-            }
-            root = DH_ID(DefhCells::pop(h.heap, nheap));
-        }
-        h.nnodes = nnodes; h.root = root;
-    }
+    // ---- code lengths: the reference heap, leaves enqueued in symbol order (one lane; <= 285 merges); one leaf: one bit
+    if (tid == 0) huff_merge(s_hist, DEFH_NSYM, h);
     __syncthreads();
-    for (int sy = tid; sy < DEFH_NSYM; sy += 64) {
-        const int leaf = h.leaf_of[sy];
-        if (leaf < 0) continue;
-        uint32_t len = 0;
-        if (h.nnodes == 1) len = 1;
-        else for (int node = leaf; node != h.root; node = h.parent[node]) ++len;
-        s_len[sy] = (uint8_t)len;
-    }
+    for (int sy = tid; sy < DEFH_NSYM; sy += 64) s_len[sy] = (uint8_t)(h.nnodes == 1 ? (h.leaf_of[sy] >= 0 ? 1u : 0u) : huff_depth(h, sy));
     __syncthreads();
     // ---- the record's size, while the tally is still there (s_hist becomes s_code below): 286 multiply-adds over the wave
     {
@@ -170,8 +103,8 @@ void k_defh_encode(const uint32_t *__restrict__ trec_all, const uint32_t *__rest
 {
     __shared__ uint32_t s_code[DEFH_NSYM + 2];
     __shared__ __attribute__((aligned(16))) uint8_t s_len[DEFH_NSYM + 2];
-    __shared__ uint32_t s_scan[DEFH_THREADS / 64 + 2];
-    __shared__ uint32_t s_stage[DEFH_THREADS * DEFH_PER * DEFH_MAXBITS / 32 + 8];
+    typedef BitPacker<DEFH_THREADS, DEFH_MAXBITS, true, true> Packer;           // MSB first, stores held below wlim
+    __shared__ uint32_t s_scan[Packer::SCAN_WORDS], s_stage[Packer::STAGE_WORDS];
 
     const int tid = threadIdx.x;
     const uint32_t lb = blockIdx.x;
@@ -194,64 +127,34 @@ void k_defh_encode(const uint32_t *__restrict__ trec_all, const uint32_t *__rest
     uint32_t *words = out + DEFH_HDR / 4;
     const uint64_t wlim = lim > DEFH_HDR / 4 ? lim - DEFH_HDR / 4 : 0;   // payload words [0, wlim) are inside the buffer
 
-    // ---- pack, DEFH_THREADS * DEFH_PER tokens per round; a thread owns DEFH_PER consecutive tokens
-    uint64_t qbase = 0;
-    uint32_t carry = 0;
-    // (the next round's records are in flight while this round is packed: a round is three barriers and one HBM round trip)
-    uint4 nrv = make_uint4(0, 0, 0, 0);
-    if ((uint32_t)tid * DEFH_PER < ntok) nrv = *reinterpret_cast<const uint4 *>(trec + (uint32_t)tid * DEFH_PER);
-    for (uint32_t t0 = 0; t0 < ntok; t0 += DEFH_THREADS * DEFH_PER) {
-        const uint32_t t = t0 + (uint32_t)tid * DEFH_PER;
-        const uint4 rv = nrv;                                              // the token array is 65536 words: in bounds
-        if (t + DEFH_THREADS * DEFH_PER < ntok) nrv = *reinterpret_cast<const uint4 *>(trec + t + DEFH_THREADS * DEFH_PER);
+    // ---- pack, DEFH_THREADS * 4 tokens per round; a thread owns 4 consecutive tokens (huff_enc.h)
+    Packer pk(s_stage, s_scan, 0, 0u, trec, ntok);
+    for (uint32_t t0 = 0; t0 < ntok; t0 += DEFH_THREADS * 4) {
+        const uint32_t t = t0 + (uint32_t)tid * 4;
+        const uint4 rv = pk.records(trec, t, ntok);
         const uint32_t r[4] = {rv.x, rv.y, rv.z, rv.w};
-        uint32_t c_v[4], c_k[4], x_v[4], x_k[4], mine = 0;
+        uint32_t v[8], nb[8], mine = 0;                                    // per token: the symbol's code, then offset and length bits
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            c_k[k] = 0; x_k[k] = 0; c_v[k] = 0; x_v[k] = 0;
+            nb[2 * k] = 0; nb[2 * k + 1] = 0; v[2 * k] = 0; v[2 * k + 1] = 0;
             if (t + k < ntok) {
                 const uint32_t sym = symbol_of(r[k]);
-                c_v[k] = s_code[sym]; c_k[k] = s_len[sym];
+                v[2 * k] = s_code[sym]; nb[2 * k] = s_len[sym];
                 if (r[k] >> 31) {
                     const uint32_t d = r[k] & 0xFFFFu, nx = 15u - clz16(d);
-                    x_v[k] = ((d - (1u << nx)) << 5) | ((r[k] >> 16) & 31u);
-                    x_k[k] = nx + 5u;
+                    v[2 * k + 1] = ((d - (1u << nx)) << 5) | ((r[k] >> 16) & 31u);
+                    nb[2 * k + 1] = nx + 5u;
                 }
-                mine += c_k[k] + x_k[k];
+                mine += nb[2 * k] + nb[2 * k + 1];
             }
         }
-        uint32_t total;
-        uint32_t rel = block_exclusive_scan<uint32_t>(mine, OpAddU32(), 0u, s_scan, &total);
-        const uint64_t w0 = qbase >> 5;
-        const uint32_t sh0 = (uint32_t)(qbase & 31u);
-        const uint32_t nwords = (sh0 + total + 31u) >> 5;
-        for (uint32_t i = tid; i < nwords + 1; i += DEFH_THREADS) s_stage[i] = (i == 0) ? carry : 0u;
-        __syncthreads();
-        rel += sh0;
-        auto put = [&](uint32_t v, uint32_t k) {                        // MSB first: k <= 32 bits at stage bit `rel`
-            if (!k) return;
-            const uint32_t wi = rel >> 5, sh = rel & 31u;
-            const uint64_t x = (uint64_t)v << (64u - k - sh);
-            atomicOr(&s_stage[wi], (uint32_t)(x >> 32));
-            if ((uint32_t)x) atomicOr(&s_stage[wi + 1], (uint32_t)x);
-            rel += k;
-        };
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { put(c_v[k], c_k[k]); put(x_v[k], x_k[k]); }
-        __syncthreads();
-        const uint32_t ncomplete = (sh0 + total) >> 5;
-        for (uint32_t i = tid; i < ncomplete; i += DEFH_THREADS) if (w0 + i < wlim) words[w0 + i] = s_stage[i];
-        carry = s_stage[ncomplete];
-        qbase += total;
-        __syncthreads();
+        pk.round(v, nb, mine, words, wlim);
     }
-    if (tid == 0 && (qbase & 31u) && (qbase >> 5) < wlim) words[qbase >> 5] = carry;
+    if (tid == 0 && (pk.qbase & 31u) && (pk.qbase >> 5) < wlim) words[pk.qbase >> 5] = pk.carry;
 }
 
 // The entropy stage of one batch, on one stream: lengths (+ sizes into block_bits), the scan that turns block_bits into offsets
 // in place and publishes the block table (lz_emit.hip), then the pack into the caller's stream at *base_bits + offset.
-void lz_launch_scan_blocks(uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits, uint64_t *excl_global, hipStream_t s);
-
 void defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits,
                         uint64_t *excl_global, uint8_t *d_out, uint64_t cap_bytes, hipStream_t s)
 {
@@ -364,8 +267,6 @@ void k_defh_decode(const uint8_t *__restrict__ stream, uint64_t stream_bytes, co
     if (bad) { if (lane == 0) atomicOr(err, 1u); return; }
     ring.finish(n);
 }
-
-mi_status lz_check_params(const mi_lz_params *p);
 
 extern "C" uint64_t mi_deflate_h_bound_bytes(uint64_t n, const mi_lz_params *p)
 {

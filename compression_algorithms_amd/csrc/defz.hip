@@ -9,7 +9,7 @@
 // 000 + pad + 00 00 FF FF).  Records are whole bytes and independent: the block table gives byte-aligned restart points.
 // The stream ends with 03 00 (a final fixed block holding only end-of-block).  include/mi_codec.h has the contract.
 //
-// Code lengths: the reference heap of k_defh_lengths (leaves in symbol order, heap_cells.h), then, where a code is longer
+// Code lengths: the reference heap mode H uses (huff_merge in huff_enc.h: leaves in symbol order), then, where a code is longer
 // than the limit (15; 7 for the code-length code), a deterministic repair: every length above the limit is clamped, codes
 // are moved one level down from the deepest level above the limit that has one until the Kraft sum is <= 1, then one level
 // up from the deepest level whose step still fits until it is exactly 1, and the new lengths are dealt out in the order of
@@ -17,14 +17,15 @@
 //
 //   k_defz_plan     one wave per block: tally of the RFC alphabets from the token records (with the clip), the three
 //                   length-limited codes, the run-length coded header, the block type; tables and header bits -> the slot
-//   k_defz_encode   one workgroup per block: header + tokens + end-of-block + sync flush, LSB first, into the slot (or the
+//   k_defz_encode   one workgroup per block: header + tokens (BitPacker, huff_enc.h) + end-of-block + sync flush, LSB first, into the slot (or the
 //                   stored form from the input); block_bits[lb] = the record's length in bits
 //   k_crc32 / k_adler32            per-workgroup partial checksums over contiguous ranges of the input
 //   k_crc32_combine / k_adler32_combine   one workgroup: the partials -> the checksum
 //   k_defz_finish   one thread: container header, the final 03 00, the trailer, the total byte count
 // k_lz_scan_blocks and k_lz_concat (lz_emit.hip) place the records, starting at the container header's bit count.
 #include "lz_common.h"
-#include "heap_cells.h"
+#include "huff_enc.h"               // the heap merge, canonical codes and the pack round, shared with defh.hip
+#include "internal.h"
 
 // slot words [DEFZ_AT, ...): what k_defz_plan hands to k_defz_encode (a record is at most 16 388 words: the stored form)
 #define DEFZ_AT        17000u
@@ -40,7 +41,6 @@ static_assert(DEFZ_HDR + DEFZ_HDR_WORDS <= LZ_DEFH_HIST_AT, "the plan's tables e
 #ifndef DEFZ_THREADS
 #define DEFZ_THREADS   256
 #endif
-#define DEFZ_PER       4                       // tokens per thread per round
 #define DEFZ_MAXBITS   48u                     // 15 + 5 (length) + 15 + 13 (distance)
 
 #define ZCK_SEG        64u                     // checksum bytes per thread and round
@@ -79,14 +79,10 @@ __device__ __forceinline__ uint32_t z_fixed_len(uint32_t s) { return s < 144u ? 
 __constant__ uint8_t kOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 __constant__ uint8_t kGzip[10] = {0x1F, 0x8B, 0x08, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0xFF};
 
-struct ZHeap {
-    int16_t  parent[2 * 288];
-    uint32_t heap[288 + 2];                   // frequency << 10 | node id (frequencies <= 65 538, ids < 576)
-    int16_t  leaf_of[288];
+struct ZHeap : HuffHeap<288> {
     uint32_t cnt[24];                         // lengths histogram of the repair
-    int      root, nnodes, maxlen;
+    int      maxlen;
 };
-typedef HeapCells<uint32_t, 10> ZCells;
 
 // Lengths of a Huffman code over freq[0, nsym), at most `limit` bits, complete.  All 64 lanes of the (one-wave) block call it.
 __device__ void z_code_lengths(const uint32_t *freq, int nsym, uint32_t limit, uint8_t *len, ZHeap &h)
@@ -95,30 +91,12 @@ __device__ void z_code_lengths(const uint32_t *freq, int nsym, uint32_t limit, u
     for (int s = lane; s < nsym; s += 64) { h.leaf_of[s] = -1; len[s] = 0; }
     __syncthreads();
     if (lane == 0) {
-        int nheap = 0, nnodes = 0, first = -1;
-        for (int s = 0; s < nsym; ++s) {
-            const uint32_t f = freq[s];
-            if (!f) continue;
-            if (first < 0) first = s;
-            const int id = nnodes++;
-            h.parent[id] = -1; h.leaf_of[s] = (int16_t)id;
-            ZCells::push(h.heap, nheap, (f << 10) | (uint32_t)id);
-        }
-        h.root = -1;
-        if (nnodes < 2) {
+        huff_merge(freq, nsym, h);
+        if (h.nnodes < 2) {
             // zlib's build_tree: pad to two codes of length 1 with symbol 0, or 1 (2) when the used one is 0 (1)
-            const int other = nnodes == 0 ? 1 : (first < 2 ? first + 1 : 0);
-            if (nnodes == 0) first = 0;
-            len[first] = 1; len[other] = 1;
-        } else {
-            while (nheap > 1) {
-                const uint32_t lc = ZCells::pop(h.heap, nheap), rc = ZCells::pop(h.heap, nheap);
-                const int id = nnodes++;
-                h.parent[id] = -1;
-                h.parent[lc & 1023u] = (int16_t)id; h.parent[rc & 1023u] = (int16_t)id;
-                ZCells::push(h.heap, nheap, (((lc >> 10) + (rc >> 10)) << 10) | (uint32_t)id);
-            }
-            h.root = (int)(ZCells::pop(h.heap, nheap) & 1023u);
+            int first = 0;
+            while (h.nnodes && h.leaf_of[first] < 0) ++first;
+            len[first] = 1; len[h.nnodes == 0 ? 1 : (first < 2 ? first + 1 : 0)] = 1;
         }
         h.maxlen = 0;
         for (int l = 0; l < 24; ++l) h.cnt[l] = 0;
@@ -126,10 +104,8 @@ __device__ void z_code_lengths(const uint32_t *freq, int nsym, uint32_t limit, u
     __syncthreads();
     if (h.root < 0) return;                                            // (uniform) the padded case is complete already
     for (int s = lane; s < nsym; s += 64) {
-        const int leaf = h.leaf_of[s];
-        if (leaf < 0) continue;
-        uint32_t l = 0;
-        for (int node = leaf; node != h.root; node = h.parent[node]) ++l;
+        const uint32_t l = huff_depth(h, s);
+        if (!l) continue;
         len[s] = (uint8_t)l;
         atomicMax(&h.maxlen, (int)l);
         atomicAdd(&h.cnt[l < 23u ? l : 23u], 1u);
@@ -174,24 +150,10 @@ __device__ void z_code_lengths(const uint32_t *freq, int nsym, uint32_t limit, u
 // RFC 1951 3.2.2 canonical codes, bit-reversed for LSB-first packing: tab[s] = rev(code) | len << 16.  All lanes.
 __device__ void z_canonical(const uint8_t *len, int nsym, uint32_t *tab, uint32_t *s_cnt /*[16]*/, uint32_t *s_next /*[16]*/)
 {
-    const int lane = threadIdx.x;
-    if (lane < 16) s_cnt[lane] = 0;
-    __syncthreads();
-    for (int s = lane; s < nsym; s += 64) if (len[s]) atomicAdd(&s_cnt[len[s]], 1u);
-    __syncthreads();
-    if (lane == 0) { uint32_t c = 0; s_next[0] = 0; for (int l = 1; l < 16; ++l) { c = (c + (l > 1 ? s_cnt[l - 1] : 0u)) << 1; s_next[l] = c; } }
-    __syncthreads();
-    for (int s = lane; s < nsym; s += 64) {
-        const uint32_t l = len[s];
-        uint32_t v = 0;
-        if (l) {
-            uint32_t rank = 0;
-            for (int k = 0; k < s; ++k) rank += (len[k] == l);
-            v = (__builtin_bitreverse32(s_next[l] + rank) >> (32u - l)) | (l << 16);
-        }
-        tab[s] = v;
-    }
-    __syncthreads();
+    // (the limiter leaves no length above 15: no bin for longer ones)
+    huff_canonical<15, 16>(len, nsym, s_cnt, s_next, [&](int s, uint32_t l, uint32_t code) {
+        tab[s] = l ? (__builtin_bitreverse32(code) >> (32u - l)) | (l << 16) : 0u;
+    });
 }
 
 __global__ __launch_bounds__(64)
@@ -357,8 +319,8 @@ void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
                    const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
 {
     __shared__ uint32_t s_ll[288], s_dc[32];
-    __shared__ uint32_t s_scan[DEFZ_THREADS / 64 + 2];
-    __shared__ uint32_t s_stage[DEFZ_THREADS * DEFZ_PER * DEFZ_MAXBITS / 32 + 8];
+    typedef BitPacker<DEFZ_THREADS, DEFZ_MAXBITS, false, false> Packer;         // LSB first, into the block's own slot
+    __shared__ uint32_t s_scan[Packer::SCAN_WORDS], s_stage[Packer::STAGE_WORDS];
     const int tid = threadIdx.x;
     const uint32_t lb = blockIdx.x;
     const uint64_t off = (block0 + lb) * (uint64_t)block;
@@ -383,21 +345,19 @@ void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
     for (int i = tid; i < 288; i += DEFZ_THREADS) s_ll[i] = out[DEFZ_LL + i];
     if (tid < 32) s_dc[tid] = out[DEFZ_DC + tid];
     for (uint32_t i = tid; i < (hbits >> 5); i += DEFZ_THREADS) out[i] = out[DEFZ_HDR + i];      // (regions apart)
-    uint32_t carry = (hbits & 31u) ? out[DEFZ_HDR + (hbits >> 5)] : 0u;
+    const uint32_t hcarry = (hbits & 31u) ? out[DEFZ_HDR + (hbits >> 5)] : 0u;
     __syncthreads();
 
-    uint64_t qbase = hbits;
-    uint4 nrv = make_uint4(0, 0, 0, 0);
-    if ((uint32_t)tid * DEFZ_PER < ntok) nrv = *reinterpret_cast<const uint4 *>(trec + (uint32_t)tid * DEFZ_PER);
-    for (uint32_t t0 = 0; t0 < ntok; t0 += DEFZ_THREADS * DEFZ_PER) {
-        const uint32_t t = t0 + (uint32_t)tid * DEFZ_PER;
-        const uint4 rv = nrv;                                              // the token array is 65536 words: in bounds
-        if (t + DEFZ_THREADS * DEFZ_PER < ntok) nrv = *reinterpret_cast<const uint4 *>(trec + t + DEFZ_THREADS * DEFZ_PER);
+    Packer pk(s_stage, s_scan, hbits, hcarry, trec, ntok);
+    for (uint32_t t0 = 0; t0 < ntok; t0 += DEFZ_THREADS * 4) {
+        const uint32_t t = t0 + (uint32_t)tid * 4;
+        const uint4 rv = pk.records(trec, t, ntok);
         const uint32_t r[4] = {rv.x, rv.y, rv.z, rv.w};
-        uint32_t a_v[4], a_k[4], b_v[4], b_k[4], mine = 0;
+        uint32_t v[8], nbit[8], mine = 0;                                  // per token: literal or length code, then a second literal or the distance code
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            a_v[k] = 0; a_k[k] = 0; b_v[k] = 0; b_k[k] = 0;
+            uint32_t &a_v = v[2 * k], &a_k = nbit[2 * k], &b_v = v[2 * k + 1], &b_k = nbit[2 * k + 1];
+            a_v = 0; a_k = 0; b_v = 0; b_k = 0;
             if (t + k >= ntok) continue;
             const uint32_t rk = r[k];
             if (rk >> 31) {
@@ -406,51 +366,29 @@ void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
                     L = clip;
                     if (clip < 3u) {                                       // the clipped match becomes 1 or 2 literals
                         const uint32_t c0 = s_ll[src[n - clip]];
-                        a_v[k] = c0 & 0xFFFFu; a_k[k] = c0 >> 16;
-                        if (clip == 2u) { const uint32_t c1 = s_ll[src[n - 1u]]; b_v[k] = c1 & 0xFFFFu; b_k[k] = c1 >> 16; }
-                        mine += a_k[k] + b_k[k];
+                        a_v = c0 & 0xFFFFu; a_k = c0 >> 16;
+                        if (clip == 2u) { const uint32_t c1 = s_ll[src[n - 1u]]; b_v = c1 & 0xFFFFu; b_k = c1 >> 16; }
+                        mine += a_k + b_k;
                         continue;
                     }
                 }
                 uint32_t nb, xv;
                 const uint32_t cl = s_ll[z_len_code(L, nb, xv)];
-                a_v[k] = (cl & 0xFFFFu) | (xv << (cl >> 16)); a_k[k] = (cl >> 16) + nb;
+                a_v = (cl & 0xFFFFu) | (xv << (cl >> 16)); a_k = (cl >> 16) + nb;
                 const uint32_t cd = s_dc[z_dist_code(rk & 0xFFFFu, nb, xv)];
-                b_v[k] = (cd & 0xFFFFu) | (xv << (cd >> 16)); b_k[k] = (cd >> 16) + nb;
+                b_v = (cd & 0xFFFFu) | (xv << (cd >> 16)); b_k = (cd >> 16) + nb;
             } else {
                 const uint32_t c = s_ll[rk & 0xFFu];
-                a_v[k] = c & 0xFFFFu; a_k[k] = c >> 16;
+                a_v = c & 0xFFFFu; a_k = c >> 16;
             }
-            mine += a_k[k] + b_k[k];
+            mine += a_k + b_k;
         }
-        uint32_t total;
-        uint32_t rel = block_exclusive_scan<uint32_t>(mine, OpAddU32(), 0u, s_scan, &total);
-        const uint64_t w0 = qbase >> 5;
-        const uint32_t sh0 = (uint32_t)(qbase & 31u);
-        const uint32_t nwords = (sh0 + total + 31u) >> 5;
-        for (uint32_t i = tid; i < nwords + 1; i += DEFZ_THREADS) s_stage[i] = (i == 0) ? carry : 0u;
-        __syncthreads();
-        rel += sh0;
-        auto put = [&](uint32_t v, uint32_t k) {                        // LSB first: k <= 32 bits at stage bit `rel`
-            if (!k) return;
-            const uint32_t wi = rel >> 5, sh = rel & 31u;
-            atomicOr(&s_stage[wi], v << sh);
-            if (sh + k > 32u) atomicOr(&s_stage[wi + 1], v >> (32u - sh));
-            rel += k;
-        };
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { put(a_v[k], a_k[k]); put(b_v[k], b_k[k]); }
-        __syncthreads();
-        const uint32_t ncomplete = (sh0 + total) >> 5;
-        for (uint32_t i = tid; i < ncomplete; i += DEFZ_THREADS) out[w0 + i] = s_stage[i];
-        carry = s_stage[ncomplete];
-        qbase += total;
-        __syncthreads();
+        pk.round(v, nbit, mine, out);
     }
     if (tid == 0) {
         // end-of-block, then the sync flush: 000 (an empty stored block), pad to a byte, 00 00 FF FF
-        uint64_t w = qbase >> 5, acc = carry;
-        uint32_t pos = (uint32_t)(qbase & 31u);
+        uint64_t w = pk.qbase >> 5, acc = pk.carry;
+        uint32_t pos = (uint32_t)(pk.qbase & 31u);
         const uint32_t eob = s_ll[256];
         acc |= (uint64_t)(eob & 0xFFFFu) << pos;
         pos += (eob >> 16) + 3u;
@@ -706,8 +644,6 @@ mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_
     return hipGetLastError() == hipSuccess ? MI_OK : MI_ERR_HIP;
 }
 
-mi_status lz_check_params(const mi_lz_params *p);
-
 // mode Z takes the deflate flavour with distances and lengths RFC 1951 can code: wbits <= 15, lbits <= 8, blocks <= 64 KiB
 mi_status defz_check(const mi_lz_params *p, uint32_t container)
 {
@@ -746,7 +682,6 @@ extern "C" mi_status mi_adler32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n
 }
 
 // host form: copy in, encode, copy out (the mi_encode_again_if_unstable rule of mi_deflate_h_encode)
-mi_status mi_encode_again_if_unstable(mi_ctx *ctx, uint32_t seen_before, mi_status st, mi_status (*again)(void *), void *arg);     // host_api.hip
 struct DefzHostArgs { mi_ctx *ctx; const mi_lz_params *p; uint32_t container; const uint8_t *h_in; uint64_t n; uint8_t *h_out; uint64_t cap;
                       uint64_t *bits; uint64_t *out_bytes; };
 

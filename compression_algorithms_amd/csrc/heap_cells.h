@@ -1,8 +1,8 @@
 // heap_cells.h — the reference's array min-heap (algorithms/huffman/huffman.c:100-163) on ONE lane, with fewer LDS round trips.
 //
-// Both tree builders (k_huff_build, k_defh_lengths) replay the reference heap operation by operation — its tie-breaking (strict
-// '<' on the frequency in both sifts, ties keep their places) defines the codes — and both wait for one lane's chain of dependent
-// LDS reads.  A heap cell is `frequency << SH | node id`, so a comparison needs one read per node.  What this header adds
+// The tree builders (k_huff_build in huffman.hip with 64-bit cells; huff_merge in huff_enc.h with 32-bit cells, for k_defh_lengths
+// and k_defz_plan) replay the reference heap operation by operation — its tie-breaking (strict '<' on the frequency in both sifts,
+// ties keep their places) defines the codes — and all wait for one lane's chain of dependent LDS reads.  A heap cell is `frequency << SH | node id`, so a comparison needs one read per node.  What this header adds
 // (round 4): the sifts read AHEAD of their decisions.
 //   sift down  the children AND the four grandchildren of a node are loaded together (six unconditional loads, out-of-range
 //              ones replaced by an infinite cell), two levels are decided per round trip.  The step the reference takes at a

@@ -2,6 +2,7 @@
 // context's private stream, copy out, synchronise.  The PCIe-inclusive path of the drop-in
 // libraries (dropin_*.c); throughput numbers are quoted on the *_dev entry points.
 #include "common.h"
+#include "internal.h"
 #include <stdlib.h>
 
 namespace {

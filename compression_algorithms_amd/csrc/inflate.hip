@@ -16,6 +16,7 @@
 // in a CU's 160 KiB (the kernel's 97 VGPRs allow 16).  DESIGN.md 3.5 has the measured figures.
 #include "lz_common.h"
 #include "lz_decode.h"
+#include "internal.h"
 #include <stdlib.h>
 
 #ifndef INF_LL_BITS
@@ -353,8 +354,6 @@ void k_inflate_frame(const uint8_t *__restrict__ stream, uint64_t stream_bytes, 
     if (t != stream_bytes) bad = true;
     if (bad) atomicOr(err, 1u);
 }
-
-size_t defz_ws_bytes();                                                // defz.hip: the checksum partials
 
 extern "C" mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t block, const uint8_t *d_stream, uint64_t stream_bytes,
                                     const uint64_t *d_seg_bits, uint8_t *d_out, uint64_t n, uint32_t flags, void *stream)

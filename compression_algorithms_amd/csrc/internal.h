@@ -1,0 +1,73 @@
+// internal.h — every function one .hip file of libmi_codec.so defines and another calls, declared ONCE, by defining file (ctx.hip's
+// are in common.h beside mi_ctx, the public extern "C" ones in include/mi_codec.h).  Callers and definers include it.  The library
+// links -shared, which accepts undefined symbols, and a definition that differs from its declaration is an overload to C++: a
+// declaration that drifts shows as ONE undefined symbol the first time the library is loaded, whichever caller runs.
+#pragma once
+#include "lz_common.h"               // LzP, LzScratch, LzwScratch
+#include "lz2.h"                     // Lz2Scratch
+
+// ---- lz_find.hip: parameters, workspace and the stages of the match finder
+mi_status lz_check_params(const mi_lz_params *p);
+size_t    lz_scratch_bytes(uint32_t nb);
+void      lz_carve(mi_ctx *ctx, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2, int set);
+uint32_t  lz_batch_blocks(mi_ctx *ctx, uint64_t nblocks);
+bool      lz_use_v2();
+mi_status lz_find_stage_a(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
+                          const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s, hipStream_t sf, hipEvent_t ev_part, hipEvent_t ev_fb,
+                          hipEvent_t ev_wide);
+mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which);
+
+// ---- lz2_partition.hip, lz2_find.hip: the LDS-resident finder
+void      lz2_launch_partition(const uint8_t *d_in, uint64_t n, const LzP &P, const Lz2Scratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
+size_t    lz2_scratch_bytes(uint32_t nb);
+void      lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc);
+mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
+                              const Lz2Scratch &sc, hipStream_t s);
+mi_status lz2_stage_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
+                         const Lz2Scratch &sc, hipStream_t s);
+mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
+                              const Lz2Scratch &sc, hipStream_t s, bool aside);
+mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which);
+void      lz2_launch_scatter(const Lz2Scratch &sc, uint16_t *cand_by_pos, uint32_t nb, hipStream_t s);
+
+// ---- lzw.hip: the lz77 flavour on blocks above 64 KiB
+size_t    lzw_scratch_bytes(uint32_t nb, uint32_t block);
+void      lzw_carve(mi_ctx *ctx, uint32_t nb, uint32_t block, LzwScratch *sc);
+uint32_t  lzw_batch_blocks(mi_ctx *ctx, uint64_t nblocks, uint32_t block);
+mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s);
+void      lzw_launch_parse_emit(const uint8_t *d_in, uint64_t n, const LzP &P, const LzwScratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
+
+// ---- lzs.hip: the time-sliced LDS-resident finder for those blocks
+bool      lzs_applicable(const LzP &P);
+mi_status lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
+                   const LzwScratch &ws, hipStream_t s, uint32_t *flagged, const uint32_t **flag_list);
+
+// ---- lz_decode.hip; lz_emit.hip: block sizes -> offsets in place and the published table, the block decoder without its closing
+// status read (host_api.hip launches one per chunk)
+void      lz_launch_decode(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_block_bits, const LzP &P, uint8_t *d_out,
+                           uint64_t n, uint64_t nblocks, uint32_t *err, hipStream_t s);
+void      lz_launch_scan_blocks(uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits, uint64_t *excl_global, hipStream_t s);
+mi_status mi_lz_decode_launch(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_stream, uint64_t stream_bytes,
+                              const uint64_t *d_block_bits, uint8_t *d_out, uint64_t n, uint32_t *err, hipStream_t s);
+
+// ---- defh.hip: mode H — the entropy stage of one batch; the decoder without its closing status read
+void      defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits,
+                             uint64_t *excl_global, uint8_t *d_out, uint64_t cap_bytes, hipStream_t s);
+mi_status mi_deflate_h_decode_launch(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_stream, uint64_t stream_bytes,
+                                     const uint64_t *d_block_bits, uint8_t *d_out, uint64_t n, uint32_t *err, hipStream_t s);
+
+// ---- defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
+struct DefzCall { uint32_t container; uint64_t *d_out_bytes; };
+void      defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
+                             uint32_t block, uint64_t b0, uint32_t nb, hipStream_t s);
+size_t    defz_ws_bytes();                                             // the checksum partials
+mi_status defz_check(const mi_lz_params *p, uint32_t container);
+mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t *base_bits,
+                     void *zws, hipStream_t s);
+mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
+                   void *zws, uint64_t *d_out_bytes, hipStream_t s);
+
+// ---- host_api.hip: the pipelined host-buffer encode; the one-more-try rule of the host-buffer encoders
+mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_in, uint64_t n,
+                                   uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, bool *done);
+mi_status mi_encode_again_if_unstable(mi_ctx *ctx, uint32_t seen_before, mi_status st, mi_status (*again)(void *), void *arg);

@@ -26,6 +26,7 @@
 #include "lz2.h"
 #include "lz_dom.h"
 #include "lz_replay.h"
+#include "internal.h"
 #include <stdlib.h>
 
 #define RS_HEAD 0x8000u
@@ -1371,8 +1372,6 @@ extern "C" int mi_lz_debug_counters(mi_ctx *ctx, uint64_t *out32)
     (void)hipDeviceSynchronize();
     return hipMemcpy(out32, ctx->lz_dbg, 64 * 8, hipMemcpyDeviceToHost) == hipSuccess ? 1 : 0;      // 64 counters: [0..31] find / parse, [32..47] partition
 }
-
-void lz2_launch_partition(const uint8_t *d_in, uint64_t n, const LzP &P, const Lz2Scratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
 
 // stage A1: partition (also decides which blocks go to the fallback pipeline)
 mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,

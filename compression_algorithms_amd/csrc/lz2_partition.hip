@@ -18,6 +18,7 @@
 // keeps base = 0.
 #include "lz_common.h"
 #include "lz2.h"
+#include "internal.h"
 
 __global__ __launch_bounds__(1024)
 void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)

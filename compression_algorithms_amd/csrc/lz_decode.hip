@@ -11,6 +11,7 @@
 // literal units between two of them is ONE parallel LDS store.  The output passes through a small LDS ring (lz_decode.h: 8 KiB
 // by default, far matches read the output buffer), so the wave slots, not the LDS, bound how many blocks share a CU.
 #include "lz_decode.h"
+#include "internal.h"
 #include <stdlib.h>
 
 template <uint32_t RING>

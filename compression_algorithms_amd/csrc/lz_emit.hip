@@ -17,6 +17,7 @@
 //   (decoders: lz_decode.hip)
 #include "lz_common.h"
 #include "lz2.h"
+#include "internal.h"
 #include <stdlib.h>
 
 
@@ -520,46 +521,6 @@ __device__ __forceinline__ uint32_t stream_bits(const uint8_t *s, uint64_t nbyte
 // =============================================================================================
 // host side
 // =============================================================================================
-size_t   lz_scratch_bytes(uint32_t nb);
-void     lz_carve(mi_ctx *ctx, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2, int set);
-mi_status lz_find_stage_a(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                          const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s, hipStream_t sf, hipEvent_t ev_part, hipEvent_t ev_fb,
-                          hipEvent_t ev_wide);
-mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which);
-bool     lz_use_v2();
-mi_status lz_run_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                      const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s);
-mi_status lz_check_params(const mi_lz_params *p);
-mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                        const LzScratch &sc, hipStream_t s);
-uint32_t lz_batch_blocks(mi_ctx *ctx, uint64_t nblocks);
-
-void defh_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, uint32_t nb, const uint64_t *base_bits,
-                        uint64_t *excl_global, uint8_t *d_out, uint64_t cap_bytes, hipStream_t s);
-// defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
-void defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
-                        uint32_t block, uint64_t b0, uint32_t nb, hipStream_t s);
-size_t    defz_ws_bytes();
-mi_status defz_check(const mi_lz_params *p, uint32_t container);
-mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t *base_bits,
-                     void *zws, hipStream_t s);
-mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
-                   void *zws, uint64_t *d_out_bytes, hipStream_t s);
-struct DefzCall { uint32_t container; uint64_t *d_out_bytes; };
-
-// lzw.hip: the lz77 flavour on blocks above 64 KiB
-size_t    lzw_scratch_bytes(uint32_t nb, uint32_t block);
-void      lzw_carve(mi_ctx *ctx, uint32_t nb, uint32_t block, LzwScratch *sc);
-uint32_t  lzw_batch_blocks(mi_ctx *ctx, uint64_t nblocks, uint32_t block);
-mi_status lzw_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s);
-mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s);
-void      lzw_launch_parse_emit(const uint8_t *d_in, uint64_t n, const LzP &P, const LzwScratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
-void      lz_launch_decode(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_block_bits, const LzP &P, uint8_t *d_out,
-                           uint64_t n, uint64_t nblocks, uint32_t *err, hipStream_t s);      // lz_decode.hip
-extern "C" uint64_t mi_deflate_h_bound_bytes(uint64_t n, const mi_lz_params *p);
-mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_in, uint64_t n,
-                                   uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, bool *done);
-
 // mode_h = 0: the reference's token stream, packed per block into the block's slot, placed by the scan / concatenate
 // kernels.  mode_h = 1: the same tokens, entropy coded per block (defh.hip); a record's size follows from its tally and code
 // lengths and records are whole dwords, so the scan runs BEFORE the pack and the pack writes every record where it belongs:
@@ -789,7 +750,6 @@ extern "C" mi_status mi_deflate_z_encode_dev(mi_ctx *ctx, const mi_lz_params *p,
     return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, 2, &z);
 }
 
-mi_status mi_encode_again_if_unstable(mi_ctx *ctx, uint32_t seen_before, mi_status st, mi_status (*again)(void *), void *arg);     // host_api.hip
 static mi_status lz_encode_host_once(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
                                      uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits);
 struct LzHostEncArgs { mi_ctx *ctx; const mi_lz_params *p; const uint8_t *h_in; uint64_t n; uint8_t *h_out; uint64_t cap; uint64_t *bits; };

@@ -22,6 +22,7 @@
 #include "lz_common.h"
 #include "lz_replay.h"
 #include "lz2.h"
+#include "internal.h"
 #include <stdlib.h>
 
 // =============================================================================================
@@ -766,7 +767,6 @@ void k_lz_emulate_dom(LzP P, LzScratch sc, uint64_t *dbg)
 // =============================================================================================
 // host side of the match finder
 // =============================================================================================
-size_t lz2_scratch_bytes(uint32_t nb);
 size_t lz_scratch_bytes(uint32_t nb)
 {
     size_t per = (size_t)LZ_MAX_BLOCK * (2 + 2 + 8 + 8 + 2) + sizeof(LzBlockMeta) + LZ_MAX_GIANTS_PER_BLOCK * 8 +
@@ -776,17 +776,6 @@ size_t lz_scratch_bytes(uint32_t nb)
 
 mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                         const LzScratch &sc, hipStream_t s, const uint32_t *blist, const uint32_t *bcount);
-size_t lz2_scratch_bytes(uint32_t nb);
-void   lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc);
-mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                              const Lz2Scratch &sc, hipStream_t s);
-mi_status lz2_stage_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                         const Lz2Scratch &sc, hipStream_t s);
-mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                              const Lz2Scratch &sc, hipStream_t s, bool aside);
-mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which);
-void   lz2_launch_scatter(const Lz2Scratch &sc, uint16_t *cand_by_pos, uint32_t nb, hipStream_t s);
-
 bool lz_use_v2()
 {
     const char *e = getenv("MI_LZ_V2");
@@ -968,13 +957,6 @@ extern "C" mi_status mi_lz_find_all_dev(mi_ctx *ctx, const mi_lz_params *p, cons
     }
     return MI_OK;
 }
-
-
-// lzw.hip
-size_t    lzw_scratch_bytes(uint32_t nb, uint32_t block);
-void      lzw_carve(mi_ctx *ctx, uint32_t nb, uint32_t block, LzwScratch *sc);
-uint32_t  lzw_batch_blocks(mi_ctx *ctx, uint64_t nblocks, uint32_t block);
-mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s);
 
 // the same hook for blocks above 64 KiB (lz77 flavour, lzw.hip): 32-bit positions, 0xFFFFFFFF = none
 extern "C" mi_status mi_lz_find_all32_dev(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,

@@ -22,6 +22,7 @@
 // window is empty and every token is a literal.
 #include "common.h"
 #include "lz_common.h"
+#include "internal.h"
 #include <stdlib.h>
 
 #define LZOLD_TILE   1024u       // positions per workgroup: they share one staged window (2^16: 66 KiB, two workgroups per CU)
@@ -217,9 +218,6 @@ extern "C" mi_status mi_lz77_old_encode(mi_ctx *ctx, uint32_t wbits, uint32_t lb
 
 // Decoder of a WHOLE-BUFFER lz77 stream (one stream, no block table: what lz77_compress_old writes, and lz77_compress for a
 // buffer of one block): one wave, the block decoder of lz_decode.hip with the buffer as its only block (lz77.c:347-377).
-void lz_launch_decode(const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_block_bits, const LzP &P, uint8_t *d_out,
-                      uint64_t n, uint64_t nblocks, uint32_t *err, hipStream_t s);      // lz_decode.hip
-
 extern "C" mi_status mi_lz77_whole_decode_dev(mi_ctx *ctx, uint32_t wbits, uint32_t lbits, const uint8_t *d_stream, uint64_t stream_bytes,
                                               uint64_t total_bits, uint8_t *d_out, uint64_t n, void *stream)
 {

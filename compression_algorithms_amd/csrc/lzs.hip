@@ -25,6 +25,7 @@
 // A step with a cluster above 4096 events (a run of one byte value) or more than 63 parts flags the block; flagged blocks
 // are then redone by lzw.hip (whole-block clusters, any size): one by one when they are few, the whole batch otherwise.
 #include "lz_common.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <stdio.h>
 

@@ -23,6 +23,7 @@
 // round trips.  It exists so that WINDOW_BITS 16 means what it says; DESIGN.md 6 says what would make it quick.
 #include "lz_common.h"
 #include "lz_replay.h"
+#include "internal.h"
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -762,12 +763,6 @@ mi_status lzw_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, u
     return MI_OK;
 }
 
-// The time-sliced LDS-resident finder (lzs.hip) first; a batch with a block it had to flag (a cluster above its capacity: long
-// runs of one byte value) is redone here, whole-block clusters of any size.
-bool      lzs_applicable(const LzP &P);
-mi_status lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                   const LzwScratch &ws, hipStream_t s, uint32_t *flagged, const uint32_t **flag_list);
-
 // the workspace as block `lb` of the batch sees it: a one-block run of the whole-block finder then works in that block's own rows
 static LzwScratch lzw_view_at(const LzwScratch &ws, uint32_t lb)
 {
@@ -779,6 +774,8 @@ static LzwScratch lzw_view_at(const LzwScratch &ws, uint32_t lb)
     return v;                                            // (the class lists and their counters are shared: lzw_find resets them)
 }
 
+// The time-sliced LDS-resident finder (lzs.hip) first; a batch with a block it had to flag (a cluster above its capacity: long
+// runs of one byte value) is redone here, whole-block clusters of any size.
 mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s)
 {
     if (lzs_applicable(P)) {
