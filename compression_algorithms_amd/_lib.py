@@ -59,6 +59,7 @@ EXPORTS = [
     "mi_deflate_h_bound_bytes", "mi_deflate_h_encode_dev", "mi_deflate_h_decode_dev", "mi_deflate_h_encode", "mi_deflate_h_decode",
     "mi_deflate_z_bound_bytes", "mi_deflate_z_encode_dev", "mi_deflate_z_encode", "mi_crc32_dev", "mi_adler32_dev",
     "mi_inflate_dev", "mi_inflate",
+    "mi_bgzf_bound_bytes", "mi_bgzf_encode_dev", "mi_bgzf_encode", "mi_bgzf_index_dev", "mi_bgzf_inflate_dev", "mi_bgzf_inflate",
     "mi_fse_block_bound", "mi_fse_encode_dev", "mi_fse_decode_dev", "mi_fse_encode", "mi_fse_decode", "mi_fse_normalise_dev",
     "mi_set_profiling", "mi_get_kernel_times",
     "mi_multi_create", "mi_multi_destroy", "mi_multi_ndev", "mi_multi_ctx", "mi_multi_transport", "mi_multi_last_transport_error",
@@ -144,6 +145,15 @@ def lib():
             u32 = C.c_uint32
             L.mi_inflate_dev.argtypes = [vp, u32, u32, vp, u64, vp, vp, u64, u32, vp]
             L.mi_inflate.argtypes = [vp, u32, u32, vp, u64, vp, vp, u64, u32]
+        if hasattr(L, "mi_bgzf_encode_dev"):
+            u32 = C.c_uint32
+            L.mi_bgzf_bound_bytes.restype = u64
+            L.mi_bgzf_bound_bytes.argtypes = [u64, C.POINTER(LzParams)]
+            L.mi_bgzf_encode_dev.argtypes = [vp, C.POINTER(LzParams), vp, u64, vp, u64, vp, vp, vp]
+            L.mi_bgzf_encode.argtypes = [vp, C.POINTER(LzParams), vp, u64, vp, u64, vp, vp]
+            L.mi_bgzf_index_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp]
+            L.mi_bgzf_inflate_dev.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, u32, vp]
+            L.mi_bgzf_inflate.argtypes = [vp, vp, u64, vp, u64, vp, u32]
         if hasattr(L, "mi_fse_encode_dev"):
             L.mi_fse_block_bound.restype = u64
             L.mi_fse_block_bound.argtypes = [C.POINTER(FseParams)]

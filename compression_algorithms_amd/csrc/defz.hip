@@ -25,6 +25,7 @@
 // k_lz_scan_blocks and k_lz_concat (lz_emit.hip) place the records, starting at the container header's bit count.
 #include "lz_common.h"
 #include "huff_enc.h"               // the heap merge, canonical codes and the pack round, shared with defh.hip
+#include "crc32.h"                  // one workgroup's CRC-32 of a byte range, shared with bgzf.hip
 #include "internal.h"
 
 // slot words [DEFZ_AT, ...): what k_defz_plan hands to k_defz_encode (a record is at most 16 388 words: the stored form)
@@ -43,14 +44,11 @@ static_assert(DEFZ_HDR + DEFZ_HDR_WORDS <= LZ_DEFH_HIST_AT, "the plan's tables e
 #endif
 #define DEFZ_MAXBITS   48u                     // 15 + 5 (length) + 15 + 13 (distance)
 
-#define ZCK_SEG        64u                     // checksum bytes per thread and round
-#define ZCK_THREADS    256u
-#define ZCK_PIECE      (ZCK_SEG * ZCK_THREADS) // bytes per workgroup and round
+// (ZCK_SEG, ZCK_THREADS, ZCK_PIECE: crc32.h)
 #define ZCK_GRID       1024u                   // partials at most (one per workgroup)
 #define ZCK_PAIRS_AT   0u                      // checksum workspace: u32 [2 * ZCK_GRID] partials, then the result words
 #define ZCK_RESULT_AT  (2u * ZCK_GRID)
 #define ADLER_MOD      65521u
-#define CRC_POLY       0xEDB88320u             // reflected
 
 __device__ __forceinline__ uint32_t z_log2(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
 
@@ -419,83 +417,17 @@ void defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_b
 // The standard values follow at the end: CRC-32 = crc ^ (0xFFFFFFFF * x^(8n) mod P) ^ 0xFFFFFFFF,
 // Adler-32 = (s + n) mod 65521 << 16 | (1 + a) mod 65521.
 // ---------------------------------------------------------------------------------------------
-__device__ uint32_t crc_mulmod(uint32_t a, uint32_t b)            // a * b mod P, reflected (bit 31 = x^0)
-{
-    uint32_t p = 0;
-#pragma unroll 8
-    for (int i = 31; i >= 0; --i) {
-        if ((a >> i) & 1u) p ^= b;
-        b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u);
-    }
-    return p;
-}
-__device__ uint32_t crc_xpow8(uint64_t len)                         // x^(8 len) mod P
-{
-    uint32_t p = 1u << 31, sq = 1u << 23;                            // 1, x^8
-    while (len) {
-        if (len & 1u) p = crc_mulmod(sq, p);
-        len >>= 1;
-        if (len) sq = crc_mulmod(sq, sq);
-    }
-    return p;
-}
-
-// the 64 bytes of one segment (fewer at the end of the input) into a per-byte callback, 16-byte loads where aligned
-template <typename F>
-__device__ __forceinline__ void zck_segment(const uint8_t *p, uint32_t len, bool v16, F &&fn)
-{
-    if (v16 && len == ZCK_SEG) {
-        uint4 v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = reinterpret_cast<const uint4 *>(p)[q];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-#pragma unroll
-            for (int j = 0; j < 16; ++j) fn((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
-        }
-    } else {
-        for (uint32_t j = 0; j < len; ++j) fn((uint32_t)p[j]);
-    }
-}
-
+// (crc_mulmod, crc_xpow8, zck_segment and the walk of one workgroup over its range, crc_range: crc32.h)
 __global__ __launch_bounds__(ZCK_THREADS)
 void k_crc32(const uint8_t *__restrict__ in, uint64_t n, uint64_t ppg, uint32_t *__restrict__ parts)
 {
-    __shared__ uint32_t s_tab[256];
-    __shared__ uint32_t s_red[ZCK_THREADS / 64];
+    __shared__ CrcLds s_crc;
     const uint32_t tid = threadIdx.x;
-    {
-        uint32_t c = tid;
-        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? CRC_POLY : 0u);
-        s_tab[tid] = c;
-    }
-    const uint32_t kfull = crc_xpow8((uint64_t)ZCK_SEG * (ZCK_THREADS - 1u - tid));      // segment -> end of a full piece
-    const uint32_t xpiece = crc_xpow8(ZCK_PIECE);
+    crc_lds_init(s_crc, tid);
     __syncthreads();
-    const bool v16 = (((uintptr_t)in) & 15u) == 0;
     const uint64_t lo = (uint64_t)blockIdx.x * ppg * ZCK_PIECE;
     const uint64_t hi = lo + ppg * ZCK_PIECE < n ? lo + ppg * ZCK_PIECE : n;
-    uint32_t run = 0;                                                  // (thread 0) crc of [lo, base)
-    for (uint64_t base = lo; base < hi; base += ZCK_PIECE) {
-        const uint64_t pend = base + ZCK_PIECE < hi ? base + ZCK_PIECE : hi;
-        const uint64_t s0 = base + (uint64_t)tid * ZCK_SEG;
-        const uint32_t len = s0 >= pend ? 0u : (uint32_t)((pend - s0) < ZCK_SEG ? (pend - s0) : ZCK_SEG);
-        uint32_t c = 0;
-        zck_segment(in + s0, len, v16, [&](uint32_t b) { c = s_tab[(c ^ b) & 0xFFu] ^ (c >> 8); });
-        const bool full = pend - base == ZCK_PIECE;
-        if (len) c = crc_mulmod(c, full ? kfull : crc_xpow8(pend - s0 - len));
-        else c = 0;
-        for (int o = 32; o > 0; o >>= 1) c ^= __shfl_xor(c, o);
-        if ((tid & 63u) == 0) s_red[tid >> 6] = c;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t pc = 0;
-            for (uint32_t w = 0; w < ZCK_THREADS / 64; ++w) pc ^= s_red[w];
-            run = crc_mulmod(run, full ? xpiece : crc_xpow8(pend - base)) ^ pc;
-        }
-        __syncthreads();
-    }
+    const uint32_t run = crc_range(in + lo, hi > lo ? hi - lo : 0u, s_crc, tid);
     if (tid == 0) parts[blockIdx.x] = run;
 }
 

@@ -126,7 +126,10 @@ __device__ __forceinline__ void inf_dist_of(uint32_t c, uint32_t &base, uint32_t
     else { nb = (c >> 1) - 1u; base = 1u + ((2u + (c & 1u)) << nb); }
 }
 
-template <uint32_t RING>
+// DESC (BGZF, bgzf.hip): `seg_bits` points at one InfSeg descriptor per segment instead of the table — the segment's first
+// and last bit, output offset and output length; block, nseg and n_total are not used.  Every segment is a whole DEFLATE
+// stream then: its last block, and only that one, has BFINAL = 1.
+template <uint32_t RING, bool DESC = false>
 __global__ __launch_bounds__(64)
 void k_inflate(const uint8_t *__restrict__ stream, uint64_t stream_bytes, const uint64_t *__restrict__ seg_bits, uint32_t block,
                uint64_t nseg, uint8_t *__restrict__ out, uint64_t n_total, uint32_t *__restrict__ status, uint32_t *__restrict__ err)
@@ -138,14 +141,16 @@ void k_inflate(const uint8_t *__restrict__ stream, uint64_t stream_bytes, const 
     __shared__ __attribute__((aligned(4))) uint8_t s_len[288 + 32 + 4], s_cl[20];
     const uint32_t lane = threadIdx.x;
     const uint64_t sg = blockIdx.x;
-    const uint64_t off = sg * (uint64_t)block;
-    const uint32_t n = (uint32_t)((n_total - off) < block ? (n_total - off) : block);
-    const uint64_t rb = seg_bits[sg], re = seg_bits[sg + 1];
+    InfSeg d = {};
+    if constexpr (DESC) d = reinterpret_cast<const InfSeg *>(seg_bits)[sg];
+    const uint64_t off = DESC ? d.out_off : sg * (uint64_t)block;
+    const uint32_t n = DESC ? d.out_len : (uint32_t)((n_total - off) < block ? (n_total - off) : block);
+    const uint64_t rb = DESC ? d.first_bit : seg_bits[sg], re = DESC ? d.last_bit : seg_bits[sg + 1];
     // the segment must lie inside the stream, on byte boundaries: every later read is bounded by [rb, re)
     bool bad = ((rb | re) & 7u) || re < rb || re > stream_bytes * 8ull;
     if (bad) { if (lane == 0) atomicOr(err, 1u); return; }
     const uint64_t nbits = re - rb;
-    const bool may_end = nseg == 1u;                                   // the one-segment rule: BFINAL = 1 may close the segment
+    const bool may_end = DESC || nseg == 1u;                           // the one-segment rule: BFINAL = 1 may close the segment
 
     // every control value below is wave-uniform (lz_decode.h): the only memory on a token's critical path is its LUT cell
     BitsLsb br;
@@ -286,9 +291,19 @@ void k_inflate(const uint8_t *__restrict__ stream, uint64_t stream_bytes, const 
     // the segment's bits are used up exactly (after BFINAL = 1: up to the padding of its last byte), and so is its output
     if (final_seen ? ((pos + 7u) & ~7ull) != nbits : pos != nbits) bad = true;
     if (o != n) bad = true;
+    if (DESC && !final_seen) bad = true;
     if (bad) { if (lane == 0) atomicOr(err, 1u); return; }
     ring.finish(n);
-    if (final_seen && lane == 0) status[INF_WS_FINAL] = 1u;
+    if (!DESC && final_seen && lane == 0) status[INF_WS_FINAL] = 1u;
+}
+
+// BGZF: one wave per member descriptor (the caller has checked every descriptor against the stream and the output range)
+void inflate_launch_segments(const uint8_t *d_stream, uint64_t stream_bytes, const InfSeg *d_seg, uint32_t nseg, uint8_t *d_out,
+                             uint32_t *err, hipStream_t s)
+{
+    const uint64_t *desc = reinterpret_cast<const uint64_t *>(d_seg);
+    if (nseg >= 1024u) hipLaunchKernelGGL((k_inflate<4096u, true>), dim3(nseg), dim3(64), 0, s, d_stream, stream_bytes, desc, 0u, (uint64_t)nseg, d_out, (uint64_t)0, (uint32_t *)nullptr, err);
+    else hipLaunchKernelGGL((k_inflate<32768u, true>), dim3(nseg), dim3(64), 0, s, d_stream, stream_bytes, desc, 0u, (uint64_t)nseg, d_out, (uint64_t)0, (uint32_t *)nullptr, err);
 }
 
 // The frame around the segments, read by one lane: bytes past the stream read as zero and count as corrupt.

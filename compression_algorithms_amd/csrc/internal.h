@@ -57,7 +57,7 @@ mi_status mi_deflate_h_decode_launch(mi_ctx *ctx, const mi_lz_params *p, const u
                                      const uint64_t *d_block_bits, uint8_t *d_out, uint64_t n, uint32_t *err, hipStream_t s);
 
 // ---- defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
-struct DefzCall { uint32_t container; uint64_t *d_out_bytes; };
+struct DefzCall { uint32_t container; uint64_t *d_out_bytes; bool bgzf = false; };   // bgzf: every record framed as a gzip member
 void      defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
                              uint32_t block, uint64_t b0, uint32_t nb, hipStream_t s);
 size_t    defz_ws_bytes();                                             // the checksum partials
@@ -66,6 +66,16 @@ mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint6
                      void *zws, hipStream_t s);
 mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
                    void *zws, uint64_t *d_out_bytes, hipStream_t s);
+
+// ---- inflate.hip: k_inflate over segment descriptors (BGZF members) instead of a table of restart points
+struct InfSeg { uint64_t first_bit, last_bit, out_off; uint32_t out_len, crc; };   // crc: the member's trailer, for bgzf.hip
+void      inflate_launch_segments(const uint8_t *d_stream, uint64_t stream_bytes, const InfSeg *d_seg, uint32_t nseg, uint8_t *d_out,
+                                  uint32_t *err, hipStream_t s);
+
+// ---- bgzf.hip: the member framing of one batch of mode-Z records in their slots; the EOF member and the total
+void      bgzf_launch_frame(uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n, uint32_t block, uint64_t b0,
+                            uint32_t nb, hipStream_t s);
+mi_status bgzf_end(mi_ctx *ctx, uint8_t *d_out, const uint64_t *d_member_bits, uint64_t nblocks, uint64_t *d_out_bytes, hipStream_t s);
 
 // ---- host_api.hip: the pipelined host-buffer encode; the one-more-try rule of the host-buffer encoders
 mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_in, uint64_t n,

@@ -589,6 +589,7 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
     if (z) {
         st = defz_begin(ctx, z->container, d_in, n, d_out, base_bits, zws, s);       // (the base starts at the header's bits)
         if (st) return st;
+        if (nblocks == 0 && z->bgzf) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return bgzf_end(ctx, d_out, d_block_bits, 0, z->d_out_bytes, s); }
         if (nblocks == 0) return defz_end(ctx, z->container, d_out, d_block_bits, 0, n, zws, z->d_out_bytes, s);
     } else MI_HIP(ctx, hipMemsetAsync(base_bits, 0, 8, s));
     if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return MI_OK; }
@@ -606,8 +607,14 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
             mi_prof_scope ph(ctx, "k_defh_encode", sp, (uint64_t)nb * P.block);
             defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, base_bits, d_block_bits + b0, d_out, cap_bytes, sp);
         } else if (mode_h == 2) {
-            mi_prof_scope ph(ctx, "k_defz_encode", sp, (uint64_t)nb * P.block);
-            defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp);
+            {
+                mi_prof_scope ph(ctx, "k_defz_encode", sp, (uint64_t)nb * P.block);
+                defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp);
+            }
+            if (z->bgzf) {
+                mi_prof_scope pf(ctx, "k_bgzf_frame", sp, (uint64_t)nb * P.block);
+                bgzf_launch_frame(sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp);
+            }
         }
         if (mode_h != 1) {
             hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, sp, sc[k].block_bits, nb, base_bits, excl_local, d_block_bits + b0);
@@ -723,6 +730,7 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
         MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_fork, 0));
     }
     MI_HIP(ctx, hipGetLastError());
+    if (z && z->bgzf) return bgzf_end(ctx, d_out, d_block_bits, nblocks, z->d_out_bytes, s);
     if (z) return defz_end(ctx, z->container, d_out, d_block_bits, nblocks, n, zws, z->d_out_bytes, s);
     return MI_OK;
 }
@@ -748,6 +756,19 @@ extern "C" mi_status mi_deflate_z_encode_dev(mi_ctx *ctx, const mi_lz_params *p,
     if (cap_bytes < mi_deflate_z_bound_bytes(n, p, container)) return MI_ERR_CAPACITY;
     const DefzCall z{container, d_out_bytes};
     return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, 2, &z);
+}
+
+// BGZF (bgzf.hip has the framing): mode Z's records, each in a gzip member of its own
+extern "C" mi_status mi_bgzf_encode_dev(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n, uint8_t *d_out,
+                                        uint64_t cap_bytes, uint64_t *d_member_bits, uint64_t *d_out_bytes, void *stream)
+{
+    if (!ctx || !d_out || !d_member_bits || !d_out_bytes || (n && !d_in)) return MI_ERR_ARG;
+    mi_status st = defz_check(p, MI_CONTAINER_RAW);
+    if (st) return st;
+    if (p->block > MI_BGZF_MAX_BLOCK) return MI_ERR_ARG;
+    if (cap_bytes < mi_bgzf_bound_bytes(n, p)) return MI_ERR_CAPACITY;
+    const DefzCall z{MI_CONTAINER_RAW, d_out_bytes, true};
+    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_member_bits, stream, 2, &z);
 }
 
 static mi_status lz_encode_host_once(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,

@@ -377,3 +377,156 @@ def decompress_z_host(data, table, n, block, container="gzip", ctx=None, verify=
                           out.ctypes.data_as(C.c_void_p), n, 0 if verify else MI_INFLATE_NO_CHECKSUM)
     _lib.check(st, "mi_inflate")
     return out[:n].tobytes()
+
+
+# ---- BGZF: mode Z's records as independent gzip members that carry their own sizes (include/mi_codec.h) ------------
+BGZF_BLOCK = 65280
+BGZF_MAX_BLOCK = 65498
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+class BgzfStream:
+    """A BGZF stream on the device: `data` uint8 tensor, `member_bits` int64 tensor [nblocks+1] (bit offset of every
+    member's first byte; the last entry is the EOF member), `n` input bytes."""
+
+    def __init__(self, data, member_bits, out_bytes, n, p, ctx=None, violations_before=0):
+        self.data, self.member_bits, self._out_bytes, self.n, self.p = data, member_bits, out_bytes, n, p
+        self._ctx, self._v0 = ctx, violations_before
+
+    @property
+    def nbytes(self):
+        b = int(self._out_bytes.item())                    # (synchronises: the encoder has joined torch's stream)
+        if self._ctx is not None and self._ctx.order_violations() != self._v0:
+            self._v0 = self._ctx.order_violations()
+            raise _lib.MiError(10, "the encoder that wrote this stream reported a sort out of order")
+        return b
+
+    def tobytes(self):
+        return self.data[: self.nbytes].cpu().numpy().tobytes()
+
+
+def bound_bytes_bgzf(n, p=None):
+    """mi_bgzf_bound_bytes (0 for a parameter set BGZF does not take)"""
+    p = p or params("deflate", block=BGZF_BLOCK)
+    return int(_lib.lib().mi_bgzf_bound_bytes(n, C.byref(p)))
+
+
+def compress_bgzf(data, p=None, ctx=None, cap=None):
+    """`data` as BGZF: what bgzip -d, samtools, gzip -d and gzip.decompress read, one member per p.block (65 280) input
+    bytes, and what decompress_bgzf reads back from the bytes alone."""
+    ctx = ctx or default_context()
+    p = p or params("deflate", block=BGZF_BLOCK)
+    d_in = as_device_bytes(data, ctx.device)
+    n = d_in.numel()
+    nblocks = (n + p.block - 1) // p.block if p.block else 0
+    if cap is None:
+        cap = bound_bytes_bgzf(n, p) or 64
+    out = torch.empty(max(cap, 4), dtype=torch.uint8, device=ctx.device)
+    bits = torch.zeros(nblocks + 2, dtype=torch.int64, device=ctx.device)
+    v0 = ctx.order_violations()
+    st = ctx.L.mi_bgzf_encode_dev(ctx.h, C.byref(p), C.c_void_p(d_in.data_ptr() if n else 0), n, C.c_void_p(out.data_ptr()), cap,
+                                  C.c_void_p(bits.data_ptr()), C.c_void_p(bits[nblocks + 1:].data_ptr()), ctx.stream_ptr())
+    _lib.check(st, "mi_bgzf_encode_dev")
+    return BgzfStream(out, bits[: nblocks + 1], bits[nblocks + 1:], n, p, ctx, v0)
+
+
+def compress_bgzf_host(data, p=None, ctx=None):
+    """the host-buffer entry point (mi_bgzf_encode) -> (bytes, member table as a list)"""
+    ctx = ctx or default_context()
+    p = p or params("deflate", block=BGZF_BLOCK)
+    buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+    n = buf.size
+    nblocks = (n + p.block - 1) // p.block
+    cap = bound_bytes_bgzf(n, p)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    bits = np.zeros(nblocks + 1, dtype=np.uint64)
+    nb = C.c_uint64(0)
+    st = ctx.L.mi_bgzf_encode(ctx.h, C.byref(p), buf.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p), cap,
+                              bits.ctypes.data_as(C.c_void_p), C.byref(nb))
+    _lib.check(st, "mi_bgzf_encode")
+    return out[: nb.value].tobytes(), [int(x) for x in bits]
+
+
+class BgzfIndex(tuple):
+    """(stream_offsets, out_offsets): int64 device tensors of members + 1 entries each, the last (stream bytes, total)"""
+
+    def __new__(cls, stream_offsets, out_offsets, pairs):
+        self = super().__new__(cls, (stream_offsets, out_offsets))
+        self.pairs = pairs                                 # the [members + 1, 2] tensor mi_bgzf_inflate_dev takes
+        return self
+
+    @property
+    def members(self):
+        return self.pairs.shape[0] - 1
+
+    def to_gzi(self):
+        """htslib's .gzi: u64 count, then (compressed offset, uncompressed offset) of members 1..count, little-endian"""
+        t = self.pairs.cpu().numpy().astype("<u8")
+        count = max(self.members - 1, 0)
+        return np.array([count], dtype="<u8").tobytes() + t[1:1 + count].tobytes()
+
+
+def _bgzf_index_dev(ctx, d_stream, cap=None):
+    nbytes = d_stream.numel()
+    count = torch.zeros(2, dtype=torch.int64, device=ctx.device)
+    ptr = C.c_void_p(d_stream.data_ptr() if nbytes else 0)
+    if cap is None:
+        st = ctx.L.mi_bgzf_index_dev(ctx.h, ptr, nbytes, None, 0, C.c_void_p(count.data_ptr()), ctx.stream_ptr())
+        _lib.check(st, "mi_bgzf_index_dev")
+        cap = int(count[0])
+    pairs = torch.zeros((cap + 1, 2), dtype=torch.int64, device=ctx.device)
+    st = ctx.L.mi_bgzf_index_dev(ctx.h, ptr, nbytes, C.c_void_p(pairs.data_ptr()), cap, C.c_void_p(count.data_ptr()), ctx.stream_ptr())
+    _lib.check(st, "mi_bgzf_index_dev")
+    return pairs[: int(count[0]) + 1]
+
+
+def bgzf_index(data, ctx=None, cap_members=None):
+    """The members of a BGZF stream (bytes or a tensor), found on the GPU from the stream itself -> BgzfIndex, which unpacks
+    as (stream_offsets, out_offsets) and has .to_gzi().  cap_members=None counts first."""
+    ctx = ctx or default_context()
+    pairs = _bgzf_index_dev(ctx, as_device_bytes(data, ctx.device), cap_members)
+    return BgzfIndex(pairs[:, 0].contiguous(), pairs[:, 1].contiguous(), pairs)
+
+
+def decompress_bgzf(data, members=None, first=0, count=None, verify=True, ctx=None):
+    """Inflate BGZF on the GPU from nothing but its bytes (`data`: bytes, a tensor or a BgzfStream; e.g. a file read from
+    disk) -> uint8 device tensor.  members: a BgzfIndex from bgzf_index (made here if None); first / count: only that range
+    of members (random access)."""
+    ctx = ctx or default_context()
+    if isinstance(data, BgzfStream):
+        data = data.data[: data.nbytes]
+    d_stream = as_device_bytes(data, ctx.device)
+    if members is None:
+        members = bgzf_index(d_stream, ctx)
+    pairs = members.pairs if isinstance(members, BgzfIndex) else torch.stack([torch.as_tensor(members[0]), torch.as_tensor(members[1])], 1)
+    pairs = pairs.to(device=ctx.device, dtype=torch.int64).contiguous()
+    total = pairs.shape[0] - 1
+    if count is None:
+        count = total - first
+    if first < 0 or count < 0 or first + count > total:
+        raise ValueError(f"members [{first}, {first + count}) of {total}")
+    n = int(pairs[first + count, 1] - pairs[first, 1])
+    out = torch.empty(max(n, 1), dtype=torch.uint8, device=ctx.device)
+    st = ctx.L.mi_bgzf_inflate_dev(ctx.h, C.c_void_p(d_stream.data_ptr()), d_stream.numel(), C.c_void_p(pairs.data_ptr()), first, count,
+                                   C.c_void_p(out.data_ptr()), n, 0 if verify else MI_INFLATE_NO_CHECKSUM, ctx.stream_ptr())
+    _lib.check(st, "mi_bgzf_inflate_dev")
+    return out[:n]
+
+
+def decompress_bgzf_host(data, ctx=None, verify=True, out_cap=None):
+    """the host-buffer entry point (mi_bgzf_inflate: index + inflate), the twin of compress_bgzf_host -> bytes"""
+    ctx = ctx or default_context()
+    buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+    if out_cap is None:                                    # the total of the members' ISIZE: a count-only index call
+        count = torch.zeros(2, dtype=torch.int64, device=ctx.device)
+        d = as_device_bytes(buf, ctx.device)
+        st = ctx.L.mi_bgzf_index_dev(ctx.h, C.c_void_p(d.data_ptr() if buf.size else 0), buf.size, None, 0, C.c_void_p(count.data_ptr()),
+                                     ctx.stream_ptr())
+        _lib.check(st, "mi_bgzf_index_dev")
+        out_cap = int(count[1])
+    out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+    nb = C.c_uint64(0)
+    st = ctx.L.mi_bgzf_inflate(ctx.h, buf.ctypes.data_as(C.c_void_p), buf.size, out.ctypes.data_as(C.c_void_p), out_cap, C.byref(nb),
+                               0 if verify else MI_INFLATE_NO_CHECKSUM)
+    _lib.check(st, "mi_bgzf_inflate")
+    return out[: nb.value].tobytes()

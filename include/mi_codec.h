@@ -379,8 +379,10 @@ mi_status mi_adler32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t 
  * segment's own output range; every loop is bounded by the segment's bit or byte count.
  * mi_inflate_dev synchronises `stream` before returning; it uses the context workspace (8 KiB of
  * checksum partials): one call of a context in flight at a time.
- * Out of scope: finding restart points in a stream that comes without a table, multi-member
- * gzip, preset dictionaries, MI_FRAME_* packing of mode Z, the multi-GPU path.
+ * Out of scope here: finding restart points in a stream that comes without a table and
+ * multi-member gzip — BGZF (below) is the answer to both: members that carry their own sizes;
+ * generic multi-member gzip without 'BC' subfields stays out of scope — preset dictionaries,
+ * MI_FRAME_* packing of mode Z, the multi-GPU path.
  * ------------------------------------------------------------------------------------ */
 #define MI_INFLATE_NO_CHECKSUM 1u   /* skip the Adler-32 / CRC-32 comparison (ISIZE and the frame are still checked) */
 mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t block, const uint8_t *d_stream, uint64_t stream_bytes,
@@ -389,6 +391,83 @@ mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t block, const 
  * decode, copy out, in one piece */
 mi_status mi_inflate(mi_ctx *ctx, uint32_t container, uint32_t block, const uint8_t *h_stream, uint64_t stream_bytes,
                      const uint64_t *h_seg_bits, uint8_t *h_out, uint64_t n, uint32_t flags);
+
+/* ------------------------------------------------------------------------------------
+ * BGZF: the blocked gzip of bgzip / htslib / samtools / tabix (SAM specification, 4.1) — a
+ * sequence of complete, independent gzip members of at most 65 536 bytes, compressed and
+ * uncompressed, each carrying its own size.  gzip -d, zcat, Python's gzip module and HTTP
+ * stacks read it as plain multi-member gzip; the GPU reads it back with no side table.
+ *
+ * Written: member b holds input block b of p->block bytes —
+ *   1F 8B 08 04 00 00 00 00 00 FF 06 00 42 43 02 00   gzip, CM 8, FLG = FEXTRA, MTIME 0, XFL 0, OS 255
+ *                                                     (reproducible, like mode Z's gzip), XLEN 6, 'B' 'C', SLEN 2
+ *   BSIZE u16 little-endian                            the member's total bytes - 1
+ *   mode Z's RECORD of block b, unchanged              same tokens, clip, limiter, header rules, block-type choice
+ *   03 00                                              the final fixed block with end-of-block alone
+ *   CRC-32 of the block's input bytes, ISIZE = the block's length, both u32 little-endian
+ * then the 28-byte EOF member 1F 8B 08 04 00 00 00 00 00 FF 06 00 42 43 02 00 1B 00 03 00 and eight
+ * zero bytes.  For n = 0 the stream is that member alone.  A member is its record + 28 bytes.
+ * p: mode Z's constraints and block <= MI_BGZF_MAX_BLOCK, anything else MI_ERR_ARG: the stored form
+ * of such a block, the longest a record gets, makes a member of at most 65 536 bytes, so BSIZE
+ * always fits (no run-time check).  d_member_bits u64[nblocks+1]: entry b is the bit offset of
+ * member b's first byte (entry 0 is 0), entry nblocks that of the EOF member.  *d_out_bytes: the
+ * total length.  d_out 4-byte aligned; cap_bytes below mi_bgzf_bound_bytes is MI_ERR_CAPACITY.
+ * Asynchronous, no allocation once the workspace has grown: the encoders' contract (top of file).
+ *
+ * Index (mi_bgzf_index_dev): from offset 0 every member is read as
+ *   1F 8B, CM = 8, FLG = 4 exactly (any other flag bit is MI_ERR_CORRUPT); MTIME, XFL, OS ignored;
+ *   any XLEN; its subfields (SI1 SI2 SLEN data) in turn — the first 'B' 'C' with SLEN = 2 that lies
+ *   inside the XLEN bytes gives BSIZE; a subfield that runs past XLEN ends the search; none found
+ *   is MI_ERR_CORRUPT;
+ *   BSIZE + 1 >= XLEN + 12 + 2 + 8, and the member lies inside the stream;
+ *   ISIZE = its last four bytes, at most 65 536.
+ * The next member starts BSIZE + 1 bytes on; the stream must end exactly at a member's end (an
+ * empty stream has no members).  An EOF member is not required; empty members may stand anywhere.
+ * d_stream 4-byte aligned (the chunk scan reads aligned words), else MI_ERR_ARG, as for inflate.
+ * d_members u64[2 * (cap_members + 1)]: members + 1 pairs (stream byte offset, output byte offset),
+ * the last one (stream_bytes, total) — the content of htslib's .gzi.  d_members = NULL only counts.
+ * d_count u64[2]: members, total output bytes (both 0 on MI_ERR_CORRUPT).  More members than
+ * cap_members is MI_ERR_CAPACITY (d_count is valid, the pairs below cap_members are written).
+ * The result is that of the serial walk from offset 0 for every input — also where stored blocks
+ * hold byte-exact member headers (a BGZF file compressed again): the kernels guess a way into
+ * every 128 KiB of the stream in parallel, and a guess stands only once the walk from the chunk
+ * before it arrives exactly there; otherwise that chunk is walked again from where it did arrive.
+ *
+ * Inflate (mi_bgzf_inflate_dev): members [first_member, first_member + n_members) of the table
+ * (which holds at least first_member + n_members + 1 pairs) are written to d_out, member m at
+ * its output offset less that of first_member; out_bytes must be the range's size (an empty range:
+ * out_bytes = 0, else MI_ERR_ARG).  Random access by member.  Per member the header is read again
+ * as above and must agree with the table (BSIZE + 1 = the distance to the next pair, ISIZE = the
+ * output distance); the DEFLATE data must occupy exactly the bytes between header and trailer, end
+ * in a BFINAL = 1 block (its only one), inflate to exactly ISIZE bytes and refer to nothing before
+ * the member; all block types and the whole RFC 1951 alphabet, as mi_inflate_dev; the CRC-32 of the
+ * decoded bytes is compared with the trailer's on the device unless MI_INFLATE_NO_CHECKSUM is set.
+ * MI_ERR_CORRUPT: any of that failing, a table that is decreasing, leaves the stream or the output
+ * range or does not fill out_bytes exactly, and every condition of the mi_inflate_dev list, per
+ * member.  MI_ERR_ARG: NULL pointers, d_stream not 4-byte aligned, unknown flag bits.
+ * The table is untrusted: reads stay inside [d_stream, d_stream + stream_bytes) rounded out to whole
+ * aligned 4-byte words and inside the member's own bytes, writes inside the member's own output
+ * range, every loop is bounded.  Index and inflate synchronise `stream` before returning and use
+ * the context workspace: one call of a context in flight at a time.
+ * mi_bgzf_inflate: host buffers — copy in, index, inflate every member, copy out; out_cap below
+ * the stream's total is MI_ERR_CAPACITY; *h_out_bytes (may be NULL) = the total.
+ * ------------------------------------------------------------------------------------ */
+#define MI_BGZF_BLOCK     65280u   /* htslib's block size */
+#define MI_BGZF_MAX_BLOCK 65498u   /* largest b with b + 5 ceil(b/65535) + 5 + 2 + 26 <= 65536 */
+/* per block of b bytes b + 5 ceil(b / 65535) + 5 (mode Z's per-block bound: the stored form and its sync flush) + 2 (03 00)
+ * + 26 (header and trailer), plus the 28 bytes of the EOF member; 0 if p is not a BGZF parameter set */
+uint64_t  mi_bgzf_bound_bytes(uint64_t n, const mi_lz_params *p);
+mi_status mi_bgzf_encode_dev(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
+                             uint64_t *d_member_bits, uint64_t *d_out_bytes, void *stream);
+/* host buffers: copy in, encode, copy out; h_member_bits u64[nblocks+1]; *h_out_bytes (may be NULL) = bytes written */
+mi_status mi_bgzf_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n, uint8_t *h_out, uint64_t cap_bytes,
+                         uint64_t *h_member_bits, uint64_t *h_out_bytes);
+mi_status mi_bgzf_index_dev(mi_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes, uint64_t *d_members, uint64_t cap_members,
+                            uint64_t *d_count, void *stream);
+mi_status mi_bgzf_inflate_dev(mi_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_members,
+                              uint64_t first_member, uint64_t n_members, uint8_t *d_out, uint64_t out_bytes, uint32_t flags, void *stream);
+mi_status mi_bgzf_inflate(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint8_t *h_out, uint64_t out_cap,
+                          uint64_t *h_out_bytes, uint32_t flags);
 
 /* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is
