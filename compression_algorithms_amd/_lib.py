@@ -59,6 +59,7 @@ EXPORTS = [
     "mi_deflate_h_bound_bytes", "mi_deflate_h_encode_dev", "mi_deflate_h_decode_dev", "mi_deflate_h_encode", "mi_deflate_h_decode",
     "mi_deflate_z_bound_bytes", "mi_deflate_z_encode_dev", "mi_deflate_z_encode", "mi_crc32_dev", "mi_adler32_dev",
     "mi_inflate_dev", "mi_inflate",
+    "mi_inflate_batch_dev", "mi_inflate_batch_size_dev", "mi_inflate_batch",
     "mi_bgzf_bound_bytes", "mi_bgzf_encode_dev", "mi_bgzf_encode", "mi_bgzf_index_dev", "mi_bgzf_inflate_dev", "mi_bgzf_inflate",
     "mi_fse_block_bound", "mi_fse_encode_dev", "mi_fse_decode_dev", "mi_fse_encode", "mi_fse_decode", "mi_fse_normalise_dev",
     "mi_set_profiling", "mi_get_kernel_times",
@@ -145,6 +146,11 @@ def lib():
             u32 = C.c_uint32
             L.mi_inflate_dev.argtypes = [vp, u32, u32, vp, u64, vp, vp, u64, u32, vp]
             L.mi_inflate.argtypes = [vp, u32, u32, vp, u64, vp, vp, u64, u32]
+        if hasattr(L, "mi_inflate_batch_dev"):
+            u32 = C.c_uint32
+            L.mi_inflate_batch_dev.argtypes = [vp, u32, u64, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+            L.mi_inflate_batch_size_dev.argtypes = [vp, u32, u64, vp, vp, vp, vp, vp, u32, vp]
+            L.mi_inflate_batch.argtypes = [vp, u32, u64, vp, vp, vp, vp, vp, vp, u32]
         if hasattr(L, "mi_bgzf_encode_dev"):
             u32 = C.c_uint32
             L.mi_bgzf_bound_bytes.restype = u64

@@ -26,6 +26,7 @@
 #include "lz_common.h"
 #include "huff_enc.h"               // the heap merge, canonical codes and the pack round, shared with defh.hip
 #include "crc32.h"                  // one workgroup's CRC-32 of a byte range, shared with bgzf.hip
+#include "adler32.h"                // ... and its Adler-32 sums, shared with inflate_batch.hip
 #include "internal.h"
 
 // slot words [DEFZ_AT, ...): what k_defz_plan hands to k_defz_encode (a record is at most 16 388 words: the stored form)
@@ -48,7 +49,6 @@ static_assert(DEFZ_HDR + DEFZ_HDR_WORDS <= LZ_DEFH_HIST_AT, "the plan's tables e
 #define ZCK_GRID       1024u                   // partials at most (one per workgroup)
 #define ZCK_PAIRS_AT   0u                      // checksum workspace: u32 [2 * ZCK_GRID] partials, then the result words
 #define ZCK_RESULT_AT  (2u * ZCK_GRID)
-#define ADLER_MOD      65521u
 
 __device__ __forceinline__ uint32_t z_log2(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }
 
@@ -431,34 +431,17 @@ void k_crc32(const uint8_t *__restrict__ in, uint64_t n, uint64_t ppg, uint32_t 
     if (tid == 0) parts[blockIdx.x] = run;
 }
 
+// (the raw sums of one workgroup over its range, adler_range: adler32.h)
 __global__ __launch_bounds__(ZCK_THREADS)
 void k_adler32(const uint8_t *__restrict__ in, uint64_t n, uint64_t ppg, uint32_t *__restrict__ parts)
 {
-    __shared__ uint64_t s_red[2][ZCK_THREADS / 64];
+    __shared__ AdlerLds s_red;
     const uint32_t tid = threadIdx.x;
     const bool v16 = (((uintptr_t)in) & 15u) == 0;
     const uint64_t lo = (uint64_t)blockIdx.x * ppg * ZCK_PIECE;
     const uint64_t hi = lo + ppg * ZCK_PIECE < n ? lo + ppg * ZCK_PIECE : n;
-    uint32_t ra = 0, rs = 0;                                           // (thread 0) raw sums of [lo, base), mod 65521
-    for (uint64_t base = lo; base < hi; base += ZCK_PIECE) {
-        const uint64_t pend = base + ZCK_PIECE < hi ? base + ZCK_PIECE : hi;
-        const uint64_t s0 = base + (uint64_t)tid * ZCK_SEG;
-        const uint32_t len = s0 >= pend ? 0u : (uint32_t)((pend - s0) < ZCK_SEG ? (pend - s0) : ZCK_SEG);
-        uint32_t a = 0, s = 0;                                         // s = sum of the running a: <= 64 * 65 / 2 * 255
-        zck_segment(in + s0, len, v16, [&](uint32_t b) { a += b; s += a; });
-        // to the end of the piece: s += a * (bytes after the segment)
-        uint64_t A = a, S = (uint64_t)s + (len ? (uint64_t)a * (pend - s0 - len) : 0ull);
-        for (int o = 32; o > 0; o >>= 1) { A += __shfl_xor(A, o); S += __shfl_xor(S, o); }
-        if ((tid & 63u) == 0) { s_red[0][tid >> 6] = A; s_red[1][tid >> 6] = S; }
-        __syncthreads();
-        if (tid == 0) {
-            uint64_t pa = 0, ps = 0;
-            for (uint32_t w = 0; w < ZCK_THREADS / 64; ++w) { pa += s_red[0][w]; ps += s_red[1][w]; }
-            rs = (uint32_t)(((uint64_t)rs + (uint64_t)ra * ((pend - base) % ADLER_MOD) + ps % ADLER_MOD) % ADLER_MOD);
-            ra = (uint32_t)(((uint64_t)ra + pa) % ADLER_MOD);
-        }
-        __syncthreads();
-    }
+    uint32_t ra = 0, rs = 0;                                           // (thread 0) raw sums of [lo, hi), mod 65521
+    adler_range(in, lo, hi, v16, s_red, tid, ra, rs);
     if (tid == 0) { parts[2 * blockIdx.x] = ra; parts[2 * blockIdx.x + 1] = rs; }
 }
 

@@ -1,0 +1,289 @@
+// inflate_batch.hip — many independent DEFLATE streams (raw, zlib or gzip, one container per call) inflated in one launch:
+// every item at its own address, of its own size, into its own buffer of a given CAPACITY, with its own verdict and length
+// written on the device.  Parallel across items only: inside an item one wave decodes serially.  include/mi_codec.h has the
+// contract.
+//
+//   k_batch_hist / k_batch_scan / k_batch_scatter   an opt-in dispatch order (MI_INFLATE_BATCH_ORDER=1): items by size class
+//                     (the position of the leading one of their compressed size), the largest class first, since workgroups
+//                     start in blockIdx order; unmeasured, hence off by default
+//   k_inflate_batch<RING, COUNT_ONLY>   one wave per item: header and trailer read by the wave itself (the rules of
+//                     k_inflate_frame), then inf_blocks (inflate_core.h), k_inflate's block and token loop, with the output
+//                     limit a capacity: past it the wave goes on COUNTING without storing.  COUNT_ONLY (the size pass) counts
+//                     from the first byte and has no ring.
+//   k_inflate_batch_check   one workgroup per item that came out MI_OK: CRC-32 (crc32.h) or Adler-32 (adler32.h) of the
+//                     decoded bytes against the item's trailer
+//
+// LDS per wave: the tables of k_inflate (4 324 bytes) + the ring: 8 420 with the 4 KiB ring, 37 092 with the 32 KiB ring
+// (fewer than 1 024 items), 4 324 without one.  DESIGN.md 3.5 has the resource lines.
+#include "lz_common.h"
+#include "lz_decode.h"
+#include "inflate_core.h"
+#include "crc32.h"
+#include "adler32.h"
+#include "internal.h"
+#include <stdlib.h>
+
+#define INFB_CLASSES   33u                     // size classes: 0 (empty), then 1 + the position of the leading one, capped
+#define INFB_WS_HEAD   512u                    // bytes in front of `order`: u32 hist[64], cursor[64]
+#define INFB_MAX_BYTES 0x7FFFFFFFull           // per item, compressed and inflated: positions inside an item are 32-bit
+
+struct InfBatch {
+    const void *const *in; const uint64_t *in_bytes;
+    void *const *out; const uint64_t *out_cap;
+    uint64_t *out_bytes; uint32_t *status, *failed;
+    const uint32_t *order;                     // workgroup j takes item order[j]; NULL: item j
+    uint32_t container;
+};
+
+__device__ __forceinline__ uint32_t infb_class(uint64_t bytes)
+{
+    const uint32_t c = bytes ? 64u - (uint32_t)__clzll((long long)bytes) : 0u;
+    return c < INFB_CLASSES ? c : INFB_CLASSES - 1u;
+}
+
+__global__ __launch_bounds__(256)
+void k_batch_hist(const uint64_t *__restrict__ in_bytes, uint32_t count, uint32_t *__restrict__ hist)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) atomicAdd(&hist[infb_class(in_bytes[i])], 1u);
+}
+
+__global__ void k_batch_scan(const uint32_t *__restrict__ hist, uint32_t *__restrict__ cursor)
+{
+    uint32_t run = 0;
+    for (int c = (int)INFB_CLASSES - 1; c >= 0; --c) { cursor[c] = run; run += hist[c]; }     // the largest class first
+}
+
+__global__ __launch_bounds__(256)
+void k_batch_scatter(const uint64_t *__restrict__ in_bytes, uint32_t count, uint32_t *__restrict__ cursor, uint32_t *__restrict__ order)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) order[atomicAdd(&cursor[infb_class(in_bytes[i])], 1u)] = i;       // (< count: the cursors partition [0, count))
+}
+
+template <uint32_t RING, bool COUNT_ONLY>
+__global__ __launch_bounds__(64)
+void k_inflate_batch(InfBatch b)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_ring[COUNT_ONLY ? 16u : RING];
+    __shared__ uint16_t s_llut[1 << INF_LL_BITS], s_dlut[1 << INF_D_BITS];
+    __shared__ InfCode<288> s_ll;
+    __shared__ InfCode<32> s_dc;
+    __shared__ __attribute__((aligned(4))) uint8_t s_len[288 + 32 + 4], s_cl[20];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t item = b.order ? b.order[blockIdx.x] : blockIdx.x;
+    const uint8_t *in = reinterpret_cast<const uint8_t *>(b.in[item]);
+    const uint64_t nb = b.in_bytes[item];
+    uint8_t *out = COUNT_ONLY ? nullptr : reinterpret_cast<uint8_t *>(b.out[item]);
+    const uint64_t cap = COUNT_ONLY ? 0ull : b.out_cap[item];
+    uint32_t st = MI_OK;
+    uint64_t size = 0;
+    if ((nb && !in) || (cap && !out) || nb > INFB_MAX_BYTES || cap > INFB_MAX_BYTES) st = MI_ERR_ARG;
+    else {
+        // ---- header and trailer: every lane reads the same few bytes, all inside [in, in + nb)
+        bool bad = false;
+        auto byte = [&](uint64_t i) -> uint32_t { if (i >= nb) { bad = true; return 0u; } return in[i]; };
+        const uint64_t hb = inf_header_bytes(b.container, byte, bad);
+        const uint64_t tl = b.container == MI_CONTAINER_GZIP ? 8u : b.container == MI_CONTAINER_ZLIB ? 4u : 0u;
+        if (bad || hb + tl >= nb) st = MI_ERR_CORRUPT;                  // (no room for one byte of DEFLATE data)
+        else {
+            // the DEFLATE data lies between header and trailer and ends, padded, exactly where the trailer starts
+            const uint64_t nbits = 8ull * (nb - hb - tl);
+            OutRing<RING> ring;
+            const InfWalk w = inf_blocks<RING, true, COUNT_ONLY>(in, 8ull * hb, nbits, out, (uint32_t)cap, true, ring, s_ring, s_llut,
+                                                                 s_dlut, s_ll, s_dc, s_len, s_cl, lane);
+            if (w.big) st = MI_ERR_ARG;                                 // more than 2^31 - 1 bytes: not a batch item
+            else if (w.bad || !w.final_seen || ((w.pos + 7u) & ~7ull) != nbits) st = MI_ERR_CORRUPT;
+            else {
+                if (b.container == MI_CONTAINER_GZIP) {
+                    const uint64_t t = nb - 4u;
+                    const uint32_t isz = (uint32_t)in[t] | ((uint32_t)in[t + 1] << 8) | ((uint32_t)in[t + 2] << 16) | ((uint32_t)in[t + 3] << 24);
+                    if (isz != w.o) st = MI_ERR_CORRUPT;
+                }
+                if (st == MI_OK) {
+                    size = w.o;
+                    if constexpr (!COUNT_ONLY) {
+                        if (w.counting) st = MI_ERR_CAPACITY;
+                        else ring.finish(w.o);
+                    }
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        b.status[item] = st;
+        b.out_bytes[item] = size;
+        if (st != MI_OK && b.failed) atomicAdd(b.failed, 1u);
+    }
+}
+
+// The checksum of every item that came out MI_OK against its trailer (zlib: Adler-32 big-endian in the last four bytes; gzip:
+// CRC-32 little-endian in front of ISIZE).  One workgroup per item: an item of hundreds of megabytes belongs to mi_inflate_dev.
+__global__ __launch_bounds__(ZCK_THREADS)
+void k_inflate_batch_check(InfBatch b)
+{
+    __shared__ CrcLds s_crc;
+    __shared__ AdlerLds s_adl;
+    __shared__ uint32_t s_st;
+    const uint32_t tid = threadIdx.x, item = blockIdx.x;
+    if (tid == 0) s_st = b.status[item];
+    __syncthreads();
+    if (s_st != MI_OK) return;                                         // (the whole workgroup)
+    const uint8_t *in = reinterpret_cast<const uint8_t *>(b.in[item]);
+    const uint8_t *out = reinterpret_cast<const uint8_t *>(b.out[item]);
+    const uint64_t nb = b.in_bytes[item], n = b.out_bytes[item];
+    uint32_t have = 0, want = 0;
+    if (b.container == MI_CONTAINER_GZIP) {
+        crc_lds_init(s_crc, tid);
+        __syncthreads();
+        const uint32_t pure = crc_range(out, n, s_crc, tid);
+        if (tid == 0) {
+            const uint64_t t = nb - 8u;
+            have = crc_standard(pure, n);
+            want = (uint32_t)in[t] | ((uint32_t)in[t + 1] << 8) | ((uint32_t)in[t + 2] << 16) | ((uint32_t)in[t + 3] << 24);
+        }
+    } else {
+        uint32_t ra, rs;
+        adler_range(out, 0, n, (((uintptr_t)out) & 15u) == 0, s_adl, tid, ra, rs);
+        if (tid == 0) {
+            const uint64_t t = nb - 4u;
+            have = adler_standard(ra, rs, n);
+            want = ((uint32_t)in[t] << 24) | ((uint32_t)in[t + 1] << 16) | ((uint32_t)in[t + 2] << 8) | (uint32_t)in[t + 3];
+        }
+    }
+    if (tid == 0 && have != want) {
+        b.status[item] = MI_ERR_CORRUPT;
+        b.out_bytes[item] = 0;
+        if (b.failed) atomicAdd(b.failed, 1u);
+    }
+}
+
+static mi_status batch_launch(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in, const uint64_t *d_in_bytes,
+                              void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes, uint32_t *d_status,
+                              uint32_t *d_failed, uint32_t flags, hipStream_t s, bool count_only)
+{
+    if (!ctx || container > MI_CONTAINER_GZIP || (flags & ~MI_INFLATE_NO_CHECKSUM) || count > 0x7FFFFFFFull) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!d_in || !d_in_bytes || !d_out_bytes || !d_status || (!count_only && (!d_out || !d_out_cap))) return MI_ERR_ARG;
+    const uint32_t cnt = (uint32_t)count;
+    // The size-class dispatch order is opt-in (MI_INFLATE_BATCH_ORDER=1, read at call time) until it is measured to pay for
+    // its memset and three launches (DESIGN_HISTORY.md): by default workgroup j takes item j and no workspace is touched.
+    const char *e = getenv("MI_INFLATE_BATCH_ORDER");
+    const bool ordered = e && atoi(e) != 0;
+    mi_status st = ordered ? mi_ws_reserve(ctx, INFB_WS_HEAD + 4ull * cnt) : MI_OK;   // (allocates and synchronises only while it grows)
+    if (st) return st;
+    if (d_failed) MI_HIP(ctx, hipMemsetAsync(d_failed, 0, 4, s));
+    uint32_t *order = nullptr;
+    if (ordered) {
+        uint32_t *hist = (uint32_t *)ctx->ws, *cursor = hist + 64;
+        order = (uint32_t *)((uint8_t *)ctx->ws + INFB_WS_HEAD);
+        MI_HIP(ctx, hipMemsetAsync(hist, 0, INFB_WS_HEAD, s));
+        mi_prof_scope pr(ctx, "k_batch_order", s, 0);
+        hipLaunchKernelGGL(k_batch_hist, dim3((cnt + 255u) / 256u), dim3(256), 0, s, d_in_bytes, cnt, hist);
+        hipLaunchKernelGGL(k_batch_scan, dim3(1), dim3(1), 0, s, hist, cursor);
+        hipLaunchKernelGGL(k_batch_scatter, dim3((cnt + 255u) / 256u), dim3(256), 0, s, d_in_bytes, cnt, cursor, order);
+    }
+    InfBatch b{d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, d_failed, order, container};
+    {
+        mi_prof_scope pr(ctx, count_only ? "k_inflate_batch_size" : "k_inflate_batch", s, 0);
+        // the ring: as mi_inflate_dev — few items cannot fill the CUs anyway and get the whole 32 KiB window in LDS
+        const char *r = getenv("MI_LZ_DECODE_RING");
+        const uint32_t want = r ? (uint32_t)atoi(r) : (cnt < 1024u ? 32768u : 4096u);
+        if (count_only) hipLaunchKernelGGL((k_inflate_batch<4096u, true>), dim3(cnt), dim3(64), 0, s, b);
+        else if (want <= 4096u) hipLaunchKernelGGL((k_inflate_batch<4096u, false>), dim3(cnt), dim3(64), 0, s, b);
+        else hipLaunchKernelGGL((k_inflate_batch<32768u, false>), dim3(cnt), dim3(64), 0, s, b);
+    }
+    if (!count_only && container != MI_CONTAINER_RAW && !(flags & MI_INFLATE_NO_CHECKSUM)) {
+        mi_prof_scope pr(ctx, "k_inflate_batch_check", s, 0);
+        hipLaunchKernelGGL(k_inflate_batch_check, dim3(cnt), dim3(ZCK_THREADS), 0, s, b);
+    }
+    MI_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+
+extern "C" mi_status mi_inflate_batch_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in,
+                                          const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap,
+                                          uint64_t *d_out_bytes, uint32_t *d_status, uint32_t *d_failed, uint32_t flags, void *stream)
+{
+    return batch_launch(ctx, container, count, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, d_failed, flags,
+                        (hipStream_t)stream, false);
+}
+
+extern "C" mi_status mi_inflate_batch_size_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in,
+                                               const uint64_t *d_in_bytes, uint64_t *d_out_bytes, uint32_t *d_status,
+                                               uint32_t *d_failed, uint32_t flags, void *stream)
+{
+    return batch_launch(ctx, container, count, d_in, d_in_bytes, nullptr, nullptr, d_out_bytes, d_status, d_failed, flags,
+                        (hipStream_t)stream, true);
+}
+
+// host buffers: the items packed into one device buffer (each at a 16-byte boundary), the outputs likewise by their
+// capacities; copy up, inflate (or only size, without h_out / h_out_cap), copy down what came out MI_OK
+extern "C" mi_status mi_inflate_batch(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *h_in,
+                                      const uint64_t *h_in_bytes, void *const *h_out, const uint64_t *h_out_cap,
+                                      uint64_t *h_out_bytes, uint32_t *h_status, uint32_t flags)
+{
+    if (!ctx || container > MI_CONTAINER_GZIP || (flags & ~MI_INFLATE_NO_CHECKSUM) || count > 0x7FFFFFFFull) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_in || !h_in_bytes || !h_out_bytes || !h_status) return MI_ERR_ARG;
+    const bool size_only = !h_out || !h_out_cap;
+    // an item the kernel answers with MI_ERR_ARG takes no room here: its (bad) pointer and size go up as they are
+    auto in_ok = [&](uint64_t i) { return h_in_bytes[i] <= INFB_MAX_BYTES && (h_in[i] || !h_in_bytes[i]); };
+    auto out_ok = [&](uint64_t i) { return h_out_cap[i] <= INFB_MAX_BYTES && (h_out[i] || !h_out_cap[i]); };
+    uint64_t in_total = 0, out_total = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        if (in_ok(i)) in_total += mi_align_up(h_in_bytes[i], 16);
+        if (!size_only && out_ok(i)) out_total += mi_align_up(h_out_cap[i], 16);
+    }
+    hipStream_t s = mi_host_stream(ctx);
+    mi_status st = MI_OK;
+    const size_t arr = mi_align_up((size_t)count * 8u, 256);
+    // host staging: [in ptrs | in bytes | out ptrs | out caps | out bytes | status], the packed inputs, the packed outputs
+    uint8_t *h_arr = (uint8_t *)calloc(6, arr), *h_pack = (uint8_t *)malloc(in_total + 16), *h_res = (uint8_t *)malloc(out_total + 16);
+    uint8_t *d_arr = nullptr, *d_pack = nullptr, *d_res = nullptr;
+    if (!h_arr || !h_pack || !h_res) st = MI_ERR_NOMEM;
+    if (st == MI_OK && (hipMalloc(&d_arr, 6 * arr) != hipSuccess || hipMalloc(&d_pack, in_total + 64) != hipSuccess ||
+                        hipMalloc(&d_res, out_total + 64) != hipSuccess)) st = MI_ERR_NOMEM;
+    if (st == MI_OK) {
+        uint64_t *p_in = (uint64_t *)h_arr, *p_nb = (uint64_t *)(h_arr + arr), *p_out = (uint64_t *)(h_arr + 2 * arr),
+                 *p_cap = (uint64_t *)(h_arr + 3 * arr);
+        uint64_t at = 0, ot = 0;
+        for (uint64_t i = 0; i < count; ++i) {
+            p_nb[i] = h_in_bytes[i];
+            if (in_ok(i)) {
+                p_in[i] = (uint64_t)(uintptr_t)(d_pack + at);
+                if (h_in_bytes[i]) memcpy(h_pack + at, h_in[i], h_in_bytes[i]);
+                at += mi_align_up(h_in_bytes[i], 16);
+            } else p_in[i] = h_in[i] ? (uint64_t)(uintptr_t)d_pack : 0u;
+            if (size_only) continue;
+            p_cap[i] = h_out_cap[i];
+            if (out_ok(i)) { p_out[i] = (uint64_t)(uintptr_t)(d_res + ot); ot += mi_align_up(h_out_cap[i], 16); }
+            else p_out[i] = h_out[i] ? (uint64_t)(uintptr_t)d_res : 0u;
+        }
+        if (hipMemcpyAsync(d_arr, h_arr, 4 * arr, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
+        if (st == MI_OK && in_total && hipMemcpyAsync(d_pack, h_pack, in_total, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
+    }
+    if (st == MI_OK)
+        st = batch_launch(ctx, container, count, (const void *const *)d_arr, (const uint64_t *)(d_arr + arr),
+                          size_only ? nullptr : (void *const *)(d_arr + 2 * arr), size_only ? nullptr : (const uint64_t *)(d_arr + 3 * arr),
+                          (uint64_t *)(d_arr + 4 * arr), (uint32_t *)(d_arr + 5 * arr), nullptr, flags, s, size_only);
+    if (st == MI_OK && hipMemcpyAsync(h_arr + 4 * arr, d_arr + 4 * arr, 2 * arr, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
+    if (st == MI_OK && out_total && hipMemcpyAsync(h_res, d_res, out_total, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
+    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
+    if (st == MI_OK) {
+        const uint64_t *r_nb = (const uint64_t *)(h_arr + 4 * arr);
+        const uint32_t *r_st = (const uint32_t *)(h_arr + 5 * arr);
+        uint64_t ot = 0;
+        for (uint64_t i = 0; i < count; ++i) {
+            h_out_bytes[i] = r_nb[i];
+            h_status[i] = r_st[i];
+            if (size_only || !out_ok(i)) continue;
+            if (r_st[i] == MI_OK && r_nb[i]) memcpy(h_out[i], h_res + ot, r_nb[i]);
+            ot += mi_align_up(h_out_cap[i], 16);
+        }
+    }
+    if (st == MI_ERR_HIP && !ctx->last_hip) ctx->last_hip = (int)hipGetLastError();
+    (void)hipFree(d_arr); (void)hipFree(d_pack); (void)hipFree(d_res);
+    free(h_arr); free(h_pack); free(h_res);
+    return st;
+}

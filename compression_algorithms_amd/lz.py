@@ -530,3 +530,157 @@ def decompress_bgzf_host(data, ctx=None, verify=True, out_cap=None):
                                0 if verify else MI_INFLATE_NO_CHECKSUM)
     _lib.check(st, "mi_bgzf_inflate")
     return out[: nb.value].tobytes()
+
+
+# ---- batched inflate: many independent raw / zlib / gzip streams in one launch (include/mi_codec.h) -------------------
+def _is_packed(items):
+    return (isinstance(items, tuple) and len(items) == 2 and not isinstance(items[1], (bytes, bytearray, memoryview))
+            and not (torch.is_tensor(items[1]) and items[1].dtype == torch.uint8))
+
+
+def _nbytes(x):
+    return x.numel() if torch.is_tensor(x) else len(x)
+
+
+def _batch_check(items, caps):
+    """everything that can be refused without a device -> (packed?, offsets or None, count)"""
+    if _is_packed(items):
+        buf, offsets = items
+        off = [int(v) for v in (offsets.cpu().tolist() if torch.is_tensor(offsets) else offsets)]
+        if len(off) < 1:
+            raise ValueError("offsets needs count + 1 entries: at least one")
+        if off[0] < 0 or any(b < a for a, b in zip(off, off[1:])) or off[-1] > _nbytes(buf):
+            raise ValueError(f"offsets must not decrease and must stay inside the buffer's {_nbytes(buf)} bytes")
+        count = len(off) - 1
+    else:
+        off, count = None, len(items)
+    if caps is not None and _nbytes(caps) != count:
+        raise ValueError(f"caps has {_nbytes(caps)} entries for {count} items")
+    return off, count
+
+
+def _batch_inputs(ctx, items, off, count):
+    """-> (tensors to keep alive, int64 device tensor of pointers, int64 device tensor of sizes)"""
+    if off is not None:
+        buf = as_device_bytes(items[0], ctx.device)
+        base = buf.data_ptr()
+        ptrs, sizes, keep = [base + a for a in off[:-1]], [b - a for a, b in zip(off, off[1:])], [buf]
+    else:
+        keep, ptrs, sizes = [], [0] * count, [0] * count
+        host = [(i, bytes(x)) for i, x in enumerate(items) if not torch.is_tensor(x)]
+        if host:                                               # the host items in one buffer, one copy up
+            at, offs = 0, []
+            for _, b in host:
+                offs.append(at)
+                at += (len(b) + 15) & ~15
+            pack = np.zeros(max(at, 1), dtype=np.uint8)
+            for (_, b), a in zip(host, offs):
+                pack[a:a + len(b)] = np.frombuffer(b, dtype=np.uint8)
+            d = torch.from_numpy(pack).to(ctx.device)
+            keep.append(d)
+            for (i, b), a in zip(host, offs):
+                ptrs[i], sizes[i] = d.data_ptr() + a, len(b)
+        for i, x in enumerate(items):
+            if torch.is_tensor(x):
+                t = x.to(device=ctx.device, dtype=torch.uint8).contiguous()
+                keep.append(t)
+                ptrs[i], sizes[i] = (t.data_ptr() if t.numel() else 0), t.numel()
+    dev = lambda v: torch.tensor(v, dtype=torch.int64, device=ctx.device) if v else torch.zeros(0, dtype=torch.int64, device=ctx.device)
+    return keep, dev(ptrs), dev(sizes)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t.numel() else 0)
+
+
+def _batch_sizes_dev(ctx, c, count, d_in, d_nb):
+    sizes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    st = ctx.L.mi_inflate_batch_size_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(sizes), _ptr(status), None, 0, ctx.stream_ptr())
+    _lib.check(st, "mi_inflate_batch_size_dev")
+    return sizes[:count], status[:count]
+
+
+def inflate_batch_sizes(items, container="gzip", ctx=None):
+    """What every item of a batch inflates to, without writing a byte -> (sizes int64, status int32) device tensors.  `items`
+    as for inflate_batch.  A checksum mismatch cannot be seen here (such an item is MI_OK)."""
+    off, count = _batch_check(items, None)
+    c = CONTAINERS.get(container, container)
+    ctx = ctx or default_context()
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    out = _batch_sizes_dev(ctx, c, count, d_in, d_nb)
+    ctx.sync()                                                 # (the inputs in `keep` may go now)
+    return out
+
+
+class InflateBatch:
+    """The result of inflate_batch: `outputs` (a list of uint8 device tensors, each cut to its size; empty where the item
+    failed), `out_bytes` (int64) and `status` (int32) device tensors, `failed` (how many items are not MI_OK)."""
+
+    def __init__(self, outputs, out_bytes, status, failed):
+        self.outputs, self.out_bytes, self.status, self.failed = outputs, out_bytes, status, failed
+
+    def raise_for_status(self):
+        if self.failed:
+            st = [int(v) for v in self.status.cpu()]
+            i = next(k for k, v in enumerate(st) if v)
+            raise _lib.MiError(st[i], f"inflate_batch: {self.failed} of {len(st)} items failed, the first one item {i}")
+        return self
+
+
+def inflate_batch(items, container="gzip", caps=None, verify=True, ctx=None):
+    """Inflate many independent streams of one container ("raw", "zlib", "gzip") in one launch -> InflateBatch.
+
+    items: a list of bytes or uint8 tensors, or a pair (buffer, offsets) for a packed buffer with count + 1 offsets (item i
+    is buffer[offsets[i]:offsets[i + 1]]: no alignment needed).  caps: the output capacity of every item (list or tensor);
+    None runs the size pass first and allocates one packed output.  An item that does not fit its capacity comes back
+    MI_ERR_CAPACITY with out_bytes = the size it needs; one bad item does not spoil the rest."""
+    off, count = _batch_check(items, caps)
+    c = CONTAINERS.get(container, container)
+    ctx = ctx or default_context()
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    if caps is None:
+        d_cap = _batch_sizes_dev(ctx, c, count, d_in, d_nb)[0]
+        cap = [int(v) for v in d_cap.cpu()]
+    else:
+        cap = [int(v) for v in (caps.cpu().tolist() if torch.is_tensor(caps) else caps)]
+        d_cap = torch.tensor(cap, dtype=torch.int64, device=ctx.device) if count else torch.zeros(0, dtype=torch.int64, device=ctx.device)
+    at, offs = 0, []
+    for v in cap:
+        offs.append(at)
+        at += (min(v, 0x7FFFFFFF) + 15) & ~15                 # (a capacity above that is refused per item)
+    out = torch.empty(max(at, 16), dtype=torch.uint8, device=ctx.device)
+    d_out = torch.tensor([out.data_ptr() + a for a in offs], dtype=torch.int64, device=ctx.device) if count else d_cap
+    nbytes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+    st = ctx.L.mi_inflate_batch_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(d_out), _ptr(d_cap), _ptr(nbytes), _ptr(status),
+                                    _ptr(failed), 0 if verify else MI_INFLATE_NO_CHECKSUM, ctx.stream_ptr())
+    _lib.check(st, "mi_inflate_batch_dev")
+    ctx.sync()
+    nb, stl = [int(v) for v in nbytes[:count].cpu()], [int(v) for v in status[:count].cpu()]
+    outputs = [out[a:a + (n if s == 0 else 0)] for a, n, s in zip(offs, nb, stl)]
+    return InflateBatch(outputs, nbytes[:count], status[:count], int(failed.item()) if count else 0)
+
+
+def inflate_batch_host(items, container="gzip", ctx=None, verify=True):
+    """the host-buffer entry point (mi_inflate_batch, called once for the sizes and once to inflate, so the inputs travel to
+    the device twice: a convenience path): a list of bytes -> (list of bytes, None where the item failed; list of status
+    codes)"""
+    items = [bytes(x) for x in items]
+    count = len(items)
+    c = CONTAINERS.get(container, container)
+    ctx = ctx or default_context()
+    arrs = [np.frombuffer(b, dtype=np.uint8) for b in items]
+    h_in = (C.c_void_p * max(count, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    h_nb = (C.c_uint64 * max(count, 1))(*[a.size for a in arrs])
+    sizes, status = (C.c_uint64 * max(count, 1))(), (C.c_uint32 * max(count, 1))()
+    flags = 0 if verify else MI_INFLATE_NO_CHECKSUM
+    st = ctx.L.mi_inflate_batch(ctx.h, c, count, h_in, h_nb, None, None, sizes, status, flags)
+    _lib.check(st, "mi_inflate_batch")
+    outs = [np.zeros(max(int(sizes[i]), 1), dtype=np.uint8) for i in range(count)]
+    h_out = (C.c_void_p * max(count, 1))(*[o.ctypes.data for o in outs])
+    h_cap = (C.c_uint64 * max(count, 1))(*[int(sizes[i]) for i in range(count)])
+    st = ctx.L.mi_inflate_batch(ctx.h, c, count, h_in, h_nb, h_out, h_cap, sizes, status, flags)
+    _lib.check(st, "mi_inflate_batch")
+    return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]

@@ -24,6 +24,9 @@
  * Decoders (*_decode_dev) synchronise `stream` before returning: MI_ERR_CORRUPT is decided on the device.  They take the
  * readable length of the stream and never read outside it, whatever an (untrusted) offset table says; every decode call
  * uses its own device status word, so decodes on different streams of one context do not interfere.
+ * One exception: the batched inflate (mi_inflate_batch_dev, mi_inflate_batch_size_dev) is asynchronous on `stream` under the
+ * encoders' contract above — its verdicts are per item and stay on the device, so nothing needs a host round trip: scratch is
+ * the context workspace, the calls allocate or synchronise only while it grows, one call per context in flight at a time.
  */
 #ifndef MI_CODEC_H
 #define MI_CODEC_H
@@ -468,6 +471,69 @@ mi_status mi_bgzf_inflate_dev(mi_ctx *ctx, const uint8_t *d_stream, uint64_t str
                               uint64_t first_member, uint64_t n_members, uint8_t *d_out, uint64_t out_bytes, uint32_t flags, void *stream);
 mi_status mi_bgzf_inflate(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint8_t *h_out, uint64_t out_cap,
                           uint64_t *h_out_bytes, uint32_t flags);
+
+/* ------------------------------------------------------------------------------------
+ * Batched inflate: many independent DEFLATE streams in one launch — Parquet / ORC pages, zarr /
+ * HDF5 chunks, PNG IDAT payloads, HTTP bodies, per-record blobs.  Parallel across items only: one
+ * wave decodes an item serially, so an item of hundreds of megabytes belongs to mi_inflate_dev
+ * with a table (its checksum, too, is computed by ONE workgroup here).
+ *
+ * Every array lives on the device and has `count` entries; d_in[i] / d_out[i] are device pointers.
+ * Item i is ONE complete stream of the call's `container` (one container per call) in the bytes
+ * [d_in[i], d_in[i] + d_in_bytes[i]): the header (the rules of mi_inflate_dev: raw none; zlib CM = 8,
+ * CINFO <= 7, FCHECK, FDICT = 0; gzip 1F 8B, CM = 8, reserved flag bits zero, FEXTRA / FNAME /
+ * FCOMMENT / FHCRC skipped by their lengths, FHCRC not verified); DEFLATE blocks of any type, the
+ * last one — and only that one — with BFINAL = 1; matches may reach back across block boundaries
+ * inside the item, up to 32 768 bytes, never before the item's first byte; the padding to a byte
+ * boundary; the trailer — none (raw), Adler-32 big-endian (zlib), CRC-32 and ISIZE little-endian
+ * (gzip).  The item ends exactly at d_in_bytes[i]: a second gzip member behind the first is trailing
+ * data, MI_ERR_CORRUPT.  Multi-member items are out of scope (BGZF above reads members in parallel).
+ * No alignment is required of d_in[i] or d_out[i].  Reads stay inside the item's own bytes, rounded
+ * out to whole aligned 4-byte words; writes inside [d_out[i], d_out[i] + d_out_cap[i]); every loop
+ * is bounded by the item's bit or byte count.  Items may overlap in their inputs (pointers into one
+ * stream) but not in their outputs.  An item never influences another item's bytes or verdict.
+ *
+ * Per item, on the device: d_status[i] (an mi_status) and d_out_bytes[i] —
+ *   MI_OK            d_out_bytes[i] = the inflated size, <= d_out_cap[i]; zlib / gzip: the checksum of
+ *                    the decoded bytes matched the trailer unless MI_INFLATE_NO_CHECKSUM is set; ISIZE
+ *                    (= the size mod 2^32) is always checked.
+ *   MI_ERR_CAPACITY  the stream is well-formed but longer than d_out_cap[i]: d_out_bytes[i] = the size
+ *                    the caller must provide.  Nothing is written at or past the capacity (a token
+ *                    that does not fit is not written at all; from there the wave only counts, with
+ *                    every bound still checked); the bytes below it are unspecified; the checksum of
+ *                    such an item is not compared.
+ *   MI_ERR_CORRUPT   d_out_bytes[i] = 0: every condition of the mi_inflate_dev list, no BFINAL = 1
+ *                    block, data behind it other than padding and trailer, a bad header, ISIZE that
+ *                    differs, a checksum mismatch.
+ *   MI_ERR_ARG       d_out_bytes[i] = 0: a NULL pointer with a non-zero size; d_in_bytes[i] or
+ *                    d_out_cap[i] above 2^31 - 1 (positions inside an item are 32-bit); an item that
+ *                    inflates to more than 2^31 - 1 bytes.
+ * *d_failed (may be NULL) = the number of items whose status is not MI_OK.
+ * The call itself returns only MI_OK, MI_ERR_ARG (NULL arrays, an unknown container, unknown flag
+ * bits, count > 2^31 - 1), MI_ERR_HIP or MI_ERR_NOMEM; count == 0 is MI_OK and launches nothing.
+ * Asynchronous on `stream` (top of file): read the verdicts after mi_sync or in stream order.
+ * mi_inflate_batch_size_dev: the same walk without writing a byte — d_out_bytes[i] = what item i
+ * inflates to, d_status[i] as above except that MI_ERR_CAPACITY does not occur and that a checksum
+ * mismatch cannot be seen (such an item is MI_OK here); gzip's ISIZE is compared.
+ * Workgroup j takes item j.  MI_INFLATE_BATCH_ORDER=1 (environment, read at call time) hands the
+ * items out by size class instead (the position of the leading one of d_in_bytes[i]), the largest
+ * first, so that one large item among thousands of small ones does not start last; it costs a
+ * memset and three small launches per call and is off until measured.  No output depends
+ * on it.  The ring is chosen as in mi_inflate_dev (32 KiB below 1 024 items, else 4 KiB) and
+ * MI_LZ_DECODE_RING overrides it here as there.
+ * mi_inflate_batch: host buffers, arrays of host pointers — copy up, inflate, copy down the items
+ * that came out MI_OK; h_out = NULL or h_out_cap = NULL runs the size pass alone (h_out_bytes and
+ * h_status are filled, nothing is inflated), which is how a caller without sizes gets them — at the
+ * price of the inputs travelling to the device twice, once per call.
+ * ------------------------------------------------------------------------------------ */
+mi_status mi_inflate_batch_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in, const uint64_t *d_in_bytes,
+                               void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes, uint32_t *d_status,
+                               uint32_t *d_failed, uint32_t flags, void *stream);
+mi_status mi_inflate_batch_size_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in,
+                                    const uint64_t *d_in_bytes, uint64_t *d_out_bytes, uint32_t *d_status, uint32_t *d_failed,
+                                    uint32_t flags, void *stream);
+mi_status mi_inflate_batch(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *h_in, const uint64_t *h_in_bytes,
+                           void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status, uint32_t flags);
 
 /* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is
