@@ -154,9 +154,10 @@ __device__ void z_canonical(const uint8_t *len, int nsym, uint32_t *tab, uint32_
     });
 }
 
-__global__ __launch_bounds__(64)
-void k_defz_plan(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, const uint64_t *__restrict__ block_bits,
-                 const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
+// (the body of k_defz_plan; DESC: `in` is the batched encoder's descriptor table — lz_block_src)
+template <bool DESC>
+__device__ __forceinline__ void defz_plan_block(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, const uint64_t *__restrict__ block_bits,
+                                                const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
 {
     __shared__ uint32_t f_ll[288], f_dc[32], f_cl[20];
     __shared__ uint8_t  l_ll[288], l_dc[32], l_cl[20];
@@ -169,7 +170,9 @@ void k_defz_plan(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ s
     const int lane = threadIdx.x;
     const uint32_t lb = blockIdx.x;
     const uint64_t off = (block0 + lb) * (uint64_t)block;
-    const uint32_t n = (uint32_t)((n_total - off) < block ? (n_total - off) : block);
+    uint32_t n = (uint32_t)((n_total - off) < block ? (n_total - off) : block);
+    const uint8_t *src = nullptr;
+    if constexpr (DESC) lz_block_src<true>(in, n_total, block, block0, lb, src, n);      // (a descriptor's block)
     const uint32_t ntok = (uint32_t)block_bits[lb];                    // k_lz_parse_emit left the token count here (>= 1)
     const uint32_t *trec = trec_all + (size_t)lb * LZ_MAX_BLOCK;
     uint32_t *out = slots + (size_t)lb * LZ_SLOT_WORDS;
@@ -202,7 +205,7 @@ void k_defz_plan(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ s
             const uint32_t Lk = Lc < L ? Lc : L;
             if (Lc < L) clip = Lc;
             if (Lk >= 3u) { atomicAdd(&f_ll[z_len_code(Lk, nb, xv)], 1u); atomicAdd(&f_dc[z_dist_code(r & 0xFFFFu, nb, xv)], 1u); }
-            else for (uint32_t k = 0; k < Lk; ++k) atomicAdd(&f_ll[in[off + n - Lk + k]], 1u);
+            else for (uint32_t k = 0; k < Lk; ++k) atomicAdd(&f_ll[DESC ? src[n - Lk + k] : in[off + n - Lk + k]], 1u);
         } else atomicAdd(&f_ll[r & 0xFFu], 1u);
         f_ll[256] += 1u;                                               // end-of-block
         out[DEFZ_CLIP] = clip;
@@ -294,6 +297,19 @@ void k_defz_plan(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ s
     if (lane == 0) out[DEFZ_TYPE] = type;
 }
 
+__global__ __launch_bounds__(64)
+void k_defz_plan(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, const uint64_t *__restrict__ block_bits,
+                 const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
+{
+    defz_plan_block<false>(trec_all, slots, block_bits, in, n_total, block, block0);
+}
+__global__ __launch_bounds__(64)
+void k_defz_plan_desc(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, const uint64_t *__restrict__ block_bits,
+                      const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
+{
+    defz_plan_block<true>(trec_all, slots, block_bits, in, n_total, block, block0);
+}
+
 // byte i of the stored form of a block of n bytes (n >= 1): pieces of <= 65 535 bytes, each 00 LEN NLEN data, then the sync
 // flush 00 00 00 FF FF, then zeros
 __device__ __forceinline__ uint32_t z_stored_byte(const uint8_t *src, uint32_t n, uint32_t npieces, uint32_t i)
@@ -312,6 +328,7 @@ __device__ __forceinline__ uint32_t z_stored_byte(const uint8_t *src, uint32_t n
     }
 }
 
+template <bool DESC>
 __global__ __launch_bounds__(DEFZ_THREADS)
 void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, uint64_t *__restrict__ block_bits,
                    const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
@@ -321,9 +338,8 @@ void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
     __shared__ uint32_t s_scan[Packer::SCAN_WORDS], s_stage[Packer::STAGE_WORDS];
     const int tid = threadIdx.x;
     const uint32_t lb = blockIdx.x;
-    const uint64_t off = (block0 + lb) * (uint64_t)block;
-    const uint32_t n = (uint32_t)((n_total - off) < block ? (n_total - off) : block);
-    const uint8_t *src = in + off;
+    const uint8_t *src; uint32_t n;
+    lz_block_src<DESC>(in, n_total, block, block0, lb, src, n);
     uint32_t *out = slots + (size_t)lb * LZ_SLOT_WORDS;
     const uint32_t type = out[DEFZ_TYPE];
     if (type == 0u) {
@@ -401,10 +417,15 @@ void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
 }
 
 void defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
-                        uint32_t block, uint64_t b0, uint32_t nb, hipStream_t s)
+                        uint32_t block, uint64_t b0, uint32_t nb, bool desc, hipStream_t s)
 {
+    if (desc) {
+        hipLaunchKernelGGL(k_defz_plan_desc, dim3(nb), dim3(64), 0, s, trec, slots, block_bits, d_in, n, block, b0);
+        hipLaunchKernelGGL(k_defz_encode<true>, dim3(nb), dim3(DEFZ_THREADS), 0, s, trec, slots, block_bits, d_in, n, block, b0);
+        return;
+    }
     hipLaunchKernelGGL(k_defz_plan, dim3(nb), dim3(64), 0, s, trec, slots, block_bits, d_in, n, block, b0);
-    hipLaunchKernelGGL(k_defz_encode, dim3(nb), dim3(DEFZ_THREADS), 0, s, trec, slots, block_bits, d_in, n, block, b0);
+    hipLaunchKernelGGL(k_defz_encode<false>, dim3(nb), dim3(DEFZ_THREADS), 0, s, trec, slots, block_bits, d_in, n, block, b0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -508,8 +529,8 @@ static mi_status zck_launch(mi_ctx *ctx, bool crc, const uint8_t *d_in, uint64_t
     return hipGetLastError() == hipSuccess ? MI_OK : MI_ERR_HIP;
 }
 
-static uint32_t defz_header_bytes(uint32_t container) { return container == MI_CONTAINER_GZIP ? 10u : container == MI_CONTAINER_ZLIB ? 2u : 0u; }
-static uint32_t defz_trailer_bytes(uint32_t container) { return container == MI_CONTAINER_GZIP ? 8u : container == MI_CONTAINER_ZLIB ? 4u : 0u; }
+uint32_t defz_header_bytes(uint32_t container) { return container == MI_CONTAINER_GZIP ? 10u : container == MI_CONTAINER_ZLIB ? 2u : 0u; }
+uint32_t defz_trailer_bytes(uint32_t container) { return container == MI_CONTAINER_GZIP ? 8u : container == MI_CONTAINER_ZLIB ? 4u : 0u; }
 
 // Before the pipeline, on `s`: the words the container header shares with the first record are zeroed (k_lz_concat ORs
 // into a word it shares with what comes before it), the running base starts at the header's bit count, the checksum runs.

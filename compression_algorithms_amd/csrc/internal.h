@@ -57,15 +57,33 @@ mi_status mi_deflate_h_decode_launch(mi_ctx *ctx, const mi_lz_params *p, const u
                                      const uint64_t *d_block_bits, uint8_t *d_out, uint64_t n, uint32_t *err, hipStream_t s);
 
 // ---- defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
-struct DefzCall { uint32_t container; uint64_t *d_out_bytes; bool bgzf = false; };   // bgzf: every record framed as a gzip member
+struct DfbCall;                                                        // a batch of independent items (deflate_batch.hip, below)
+struct DefzCall { uint32_t container; uint64_t *d_out_bytes; bool bgzf = false; const DfbCall *batch = nullptr; };   // bgzf: every record framed as a gzip member
 void      defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
-                             uint32_t block, uint64_t b0, uint32_t nb, hipStream_t s);
+                             uint32_t block, uint64_t b0, uint32_t nb, bool desc, hipStream_t s);     // desc: d_in is a descriptor table
+uint32_t  defz_header_bytes(uint32_t container);
+uint32_t  defz_trailer_bytes(uint32_t container);
 size_t    defz_ws_bytes();                                             // the checksum partials
 mi_status defz_check(const mi_lz_params *p, uint32_t container);
 mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t *base_bits,
                      void *zws, hipStream_t s);
 mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
                    void *zws, uint64_t *d_out_bytes, hipStream_t s);
+
+// ---- lz_emit.hip: the encoder pipeline (modes T, H, Z, BGZF and, with z->batch, the batch); deflate_batch.hip: what a batch adds
+// to it — the descriptor table and per-block checksums in front, the placement of one pipeline batch's records, the per-item finish
+mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
+                         uint64_t *d_block_bits, void *stream, int mode_h, const DefzCall *z = nullptr);
+struct DfbCall {
+    uint32_t container; uint64_t count, max_blocks;
+    const void *const *in; const uint64_t *in_bytes; void *const *out; const uint64_t *out_cap;
+    uint64_t *out_bytes; uint32_t *status, *failed;
+};
+size_t    dfb_ws_bytes(const DfbCall &b);
+mi_status dfb_begin(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s, const uint8_t **desc);
+void      dfb_launch_place(const DfbCall &b, void *ws, const uint32_t *slots, const uint64_t *block_bits, uint64_t b0, uint32_t nb,
+                           uint64_t seq, hipStream_t s);
+mi_status dfb_end(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s);
 
 // ---- inflate.hip: k_inflate over segment descriptors (BGZF members) instead of a table of restart points
 struct InfSeg { uint64_t first_bit, last_bit, out_off; uint32_t out_len, crc; };   // crc: the member's trailer, for bgzf.hip

@@ -125,7 +125,7 @@ __device__ __forceinline__ void replay_small_reg(const uint16_t *pos, const uint
 }
 
 // one part: `item` = block | part << 16 | entries << 24 | list start << 40 (lz2.h).  CAP = LDS capacity in entries.
-template <uint32_t CAP>
+template <uint32_t CAP, bool DESC>
 __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, uint64_t n_total, const LzP &P, const Lz2Scratch &sc, uint64_t block0, const uint64_t item)
 {
     // 16 bytes per entry + radix counters
@@ -178,9 +178,10 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     const uint32_t m = (uint32_t)(item >> 24) & 0xFFFFu;
     if (m == 0) return;
     const uint32_t pstart = (uint32_t)(item >> 40), base = mt->base;
-    const uint64_t off = (block0 + lb) * (uint64_t)P.block;
     const uint32_t nblk = mt->n;
-    const uint8_t *src = in + off;
+    const uint8_t *src; uint32_t n_unused;
+    lz_block_src<DESC>(in, n_total, P.block, block0, lb, src, n_unused);
+    (void)n_unused;
     const uint32_t T = 1u << P.tbits, Tmask = T - 1u, W = 1u << P.wbits;
     uint16_t *plist = sc.plist + (size_t)lb * LZ_MAX_BLOCK + pstart;       // written here (the parse reads position / candidate lists)
     (void)n_total;
@@ -251,7 +252,9 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
         // all of a thread's words first, then the hashing: the loads are in flight together instead of one entry at a time
         constexpr uint32_t GCH = CAP / LZ2_THREADS;
         uint32_t gp[GCH], glo[GCH], ghi[GCH];
-        const bool aligned = (((uintptr_t)src) & 3u) == 0;
+        // (a descriptor's block starts anywhere: the two words are the ALIGNED ones around src + p, both inside [src, src + nblk)
+        //  rounded out to aligned words, and the shift below is the address's own — no byte-wise gather for an odd item)
+        const bool aligned = DESC || (((uintptr_t)src) & 3u) == 0;
 #pragma unroll
         for (uint32_t c = 0; c < GCH; ++c) { const uint32_t j = tid + c * LZ2_THREADS; gp[c] = j < m ? (uint32_t)s_pos[j] : 0u; if (j < m) plist[j] = (uint16_t)gp[c]; }
 #pragma unroll
@@ -719,18 +722,31 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
 // words from one L2 instead of pulling the block's 64 KiB into all eight (HBM fetch of this kernel: profiles/).
 // __launch_bounds__(512, 8): eight waves per SIMD = four workgroups per CU, together with the LDS of lz2_find_part<2048>
 // (< 40 KiB): registers above 64 VGPRs / 80 SGPRs would cap the occupancy below that (tests/test_find_budget.py)
-__global__ __launch_bounds__(LZ2_THREADS, 8)
-void k_lz2_find(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
+template <bool DESC>
+__device__ __forceinline__ void lz2_find_listed(const uint8_t *__restrict__ in, uint64_t n_total, const LzP &P, const Lz2Scratch &sc, uint64_t block0)
 {
     // the grid is a multiple of 8 (lz2_stage_find) and takes the first gridDim.x listed parts; what a batch lists beyond it
     // (more than LZ2_GRID_PARTS parts per block on average: not seen on any corpus) is k_lz2_find_wide's
     const uint32_t listed = *sc.work_count, nwork = listed < gridDim.x ? listed : gridDim.x;
     const uint32_t cpx = (nwork + 7u) >> 3, item_idx = (blockIdx.x & 7u) * cpx + (blockIdx.x >> 3);
     if ((blockIdx.x >> 3) >= cpx || item_idx >= nwork) return;
-    lz2_find_part<LZ2_CAP_S>(in, n_total, P, sc, block0, sc.work[item_idx]);
+    lz2_find_part<LZ2_CAP_S, DESC>(in, n_total, P, sc, block0, sc.work[item_idx]);
+}
+// (two plain kernels, not a kernel template: tests/test_find_budget.py finds the budgeted kernel by its name)
+__global__ __launch_bounds__(LZ2_THREADS, 8)
+void k_lz2_find(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
+{
+    lz2_find_listed<false>(in, n_total, P, sc, block0);
+}
+// ... and over the batched encoder's descriptor table (`in`: lz_block_src)
+__global__ __launch_bounds__(LZ2_THREADS, 8)
+void k_lz2_find_desc(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
+{
+    lz2_find_listed<true>(in, n_total, P, sc, block0);
 }
 
 // the parts above LZ2_CAP_S entries (rare: listed from the end of the work array backwards): a small grid that loops
+template <bool DESC>
 __global__ __launch_bounds__(LZ2_THREADS)
 void k_lz2_find_wide(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0, uint32_t covered)
 {
@@ -738,7 +754,7 @@ void k_lz2_find_wide(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     // entries fits the wide instance)
     const uint32_t nwide = sc.work_count[1], listed = sc.work_count[0], rest = listed > covered ? listed - covered : 0u;
     for (uint32_t k = blockIdx.x; k < nwide + rest; k += gridDim.x) {
-        lz2_find_part<LZ2_CAP>(in, n_total, P, sc, block0, k < nwide ? sc.work[sc.work_slots - 1u - k] : sc.work[covered + (k - nwide)]);
+        lz2_find_part<LZ2_CAP, DESC>(in, n_total, P, sc, block0, k < nwide ? sc.work[sc.work_slots - 1u - k] : sc.work[covered + (k - nwide)]);
         __syncthreads();
     }
 }
@@ -1399,7 +1415,8 @@ mi_status lz2_stage_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_
                          const Lz2Scratch &sc, hipStream_t s)
 {
     mi_prof_scope p(ctx, "k_lz2_find", s, (uint64_t)nb * P.block);
-    hipLaunchKernelGGL(k_lz2_find, dim3(lz2_find_grid(P, nb)), dim3(LZ2_THREADS), 0, s, d_in, n, P, sc, block0);
+    if (P.flags & LZP_DESC) hipLaunchKernelGGL(k_lz2_find_desc, dim3(lz2_find_grid(P, nb)), dim3(LZ2_THREADS), 0, s, d_in, n, P, sc, block0);
+    else hipLaunchKernelGGL(k_lz2_find, dim3(lz2_find_grid(P, nb)), dim3(LZ2_THREADS), 0, s, d_in, n, P, sc, block0);
     MI_HIP(ctx, hipGetLastError());
     return MI_OK;
 }
@@ -1420,7 +1437,8 @@ mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, ui
     if (aside && !prof_fb) ctx->profiling = 0;
     {
         mi_prof_scope p(ctx, "k_lz2_find_wide", s, (uint64_t)nb * P.block);
-        hipLaunchKernelGGL(k_lz2_find_wide, dim3(256), dim3(LZ2_THREADS), 0, s, d_in, n, P, sc, block0, lz2_find_grid(P, nb));
+        if (P.flags & LZP_DESC) hipLaunchKernelGGL(k_lz2_find_wide<true>, dim3(256), dim3(LZ2_THREADS), 0, s, d_in, n, P, sc, block0, lz2_find_grid(P, nb));
+        else hipLaunchKernelGGL(k_lz2_find_wide<false>, dim3(256), dim3(LZ2_THREADS), 0, s, d_in, n, P, sc, block0, lz2_find_grid(P, nb));
     }
     ctx->profiling = saved_prof;
     MI_HIP(ctx, hipGetLastError());

@@ -20,6 +20,10 @@
 #include "lz2.h"
 #include "internal.h"
 
+// (internal linkage, as the kernel had before it was a template: the LDS arrays of a template with external linkage are
+//  linkonce symbols the optimiser must keep whole — s_pstart, written and never read, came back as 520 bytes of LDS)
+namespace {
+template <bool DESC>                                 // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
 __global__ __launch_bounds__(1024)
 void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
 {
@@ -36,13 +40,12 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     const uint32_t lb = blockIdx.x;
     long long tk = clock64();
 #define PT_TICK(k) do { if (sc.dbg && tid == 0) { long long t2 = clock64(); atomicAdd((unsigned long long *)&sc.dbg[32 + (k)], (unsigned long long)(t2 - tk)); tk = t2; } } while (0)
-    const uint64_t off = (block0 + lb) * (uint64_t)P.block;
-    const uint32_t n = (uint32_t)((n_total - off) < P.block ? (n_total - off) : P.block);
-    const uint8_t *src = in + off;
+    const uint8_t *src; uint32_t n;
+    lz_block_src<DESC>(in, n_total, P.block, block0, lb, src, n);
     const uint32_t T = 1u << P.tbits, Tmask = T - 1u;
     const uint32_t gshift = P.tbits - LZ2_NG_BITS, Gw = 1u << gshift;
 
-    lz_block_to_lds(s_in, src, n, (uint32_t)tid);
+    lz_block_to_lds_of<DESC>(s_in, src, n, (uint32_t)tid);
     for (uint32_t i = tid; i < LZ2_NG; i += 1024) s_grp[i] = 0;
     for (uint32_t i = tid; i < LZ2_NG / 32; i += 1024) s_safe[i] = 0;
     if (tid == 0) { s_s0 = ~0u; s_flag = 0; }
@@ -280,10 +283,12 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     PT_TICK(6);
     if (sc.dbg && tid == 0) atomicAdd((unsigned long long *)&sc.dbg[47], 1ull);
 }
+}  // namespace
 
 void lz2_launch_partition(const uint8_t *d_in, uint64_t n, const LzP &P, const Lz2Scratch &sc, uint64_t block0, uint32_t nb, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_lz2_partition, dim3(nb), dim3(1024), 0, s, d_in, n, P, sc, block0);
+    if (P.flags & LZP_DESC) hipLaunchKernelGGL(k_lz2_partition<true>, dim3(nb), dim3(1024), 0, s, d_in, n, P, sc, block0);
+    else hipLaunchKernelGGL(k_lz2_partition<false>, dim3(nb), dim3(1024), 0, s, d_in, n, P, sc, block0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -36,6 +36,7 @@ struct LzP {
 #define LZP_ARANK 1u
 #define LZP_BREAK 2u       // TEST BUILD ONLY (-DMI_TEST_HOOKS, MI_LZ_TEST_BREAK_RANK=1): the scatter swaps the ranks of neighbouring lanes with equal digits
 #define LZP_FORCE_FB 4u    // TEST BUILD ONLY (-DMI_TEST_HOOKS, MI_LZ_TEST_FORCE_FALLBACK=1): the partition hands EVERY block to the fallback pipeline
+#define LZP_DESC 8u        // the batched encoder (deflate_batch.hip): the kernels' `in` is a table of LzBlkDesc, not the input (lz_block_src)
 
 // The stable radix scatter under LZP_ARANK ranks by the order in which ONE returning LDS add serves the lanes that hit one
 // address — lane order on gfx950, measured (scripts/micro/lds_atomic_order.hip) and probed once per context (ctx.hip), but
@@ -57,6 +58,34 @@ static inline LzP lz_params_of(mi_ctx *ctx, const mi_lz_params *p)
     if (fl && ctx->test_break_rank) fl |= LZP_BREAK;
     if (ctx->test_force_fb) fl |= LZP_FORCE_FB;
     return LzP{p->wbits, p->lbits, p->tbits, p->deflate, p->block, fl, ctx->d_order, ctx->d_stats};
+}
+
+// ---- where a block's bytes are.  One buffer: block g is in[g * block, ...) and the last one is short.  A batch of independent
+// items (deflate_batch.hip): block g is whatever descriptor g says — any address, any length 1..block, and what follows it in
+// memory is another item or nothing.  The six kernels that read input bytes take the pair from lz_block_src; DESC is a template
+// parameter, so the one-buffer instantiations are the code they were.  With DESC the kernel's `in` argument IS the table (the
+// launch sites pick the instantiation by LZP_DESC): no kernel signature changes.
+struct LzBlkDesc {
+    const uint8_t *src;    // the block's first byte
+    uint32_t n;            // its bytes, 1..block
+    uint32_t item;         // the item it belongs to; LZ_DESC_PAD: a pad block behind the batch's real ones (one zero byte, placed nowhere)
+    uint32_t blk;          // its number inside the item
+    uint32_t last;         // 1: the item's last block
+};
+#define LZ_DESC_PAD 0xFFFFFFFFu
+
+template <bool DESC>
+__device__ __forceinline__ void lz_block_src(const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0, uint32_t lb,
+                                             const uint8_t *&src, uint32_t &n)
+{
+    if constexpr (DESC) {
+        const LzBlkDesc *d = reinterpret_cast<const LzBlkDesc *>(in) + (block0 + lb);
+        src = d->src; n = d->n;
+    } else {
+        const uint64_t off = (block0 + lb) * (uint64_t)block;
+        n = (uint32_t)((n_total - off) < block ? (n_total - off) : block);
+        src = in + off;
+    }
 }
 
 // per-block record written by k_lz_sort_home
@@ -180,6 +209,79 @@ __device__ __forceinline__ void lz_block_to_lds(uint8_t *s_dst, const uint8_t *_
             for (uint32_t b = 0; b < 16; ++b) s_dst[i + b] = (i + b < n) ? src[i + b] : (uint8_t)0;
         }
     }
+}
+
+// ---- the same for a block at ANY address (the descriptor path: in a packed page buffer almost no item starts on a 16-byte
+// boundary, and the byte-wise branch above is 16 loads where one would do).  The bytes src[i, i + 16) lie in two aligned
+// 16-byte words; both are loaded whole and shifted in registers.  Only words that hold at least one byte of the block are
+// read — reads stay inside the block's bytes rounded out to aligned 16-byte words — and bytes at or past n come out zero.
+// i is a multiple of 16 below n (callers clamp): the shift is then the same for every thread of the workgroup.
+struct LzVec2 { uint4 lo, hi; };
+__device__ __forceinline__ LzVec2 lz_load16_pair(const uint8_t *__restrict__ src, uint32_t n, uint32_t i)
+{
+    const uintptr_t a = (uintptr_t)(src + i);
+    const uint32_t sh = (uint32_t)(a & 15u);
+    const uint4 *lo = reinterpret_cast<const uint4 *>(a - sh);
+    const uint32_t want = (n - i) < 16u ? (n - i) : 16u;             // bytes of the block in this piece, >= 1
+    LzVec2 v;
+    v.lo = lo[0];
+    v.hi = lo[sh + want > 16u ? 1 : 0];                              // (the same word again where the piece ends inside the first)
+    return v;
+}
+__device__ __forceinline__ uint4 lz_shift16(const LzVec2 &v, uint32_t sh /* src & 15 */, uint32_t valid /* bytes to keep, 0..16 */)
+{
+    const uint32_t w[8] = {v.lo.x, v.lo.y, v.lo.z, v.lo.w, v.hi.x, v.hi.y, v.hi.z, v.hi.w};
+    const uint32_t ws = sh >> 2, bs = (sh & 3u) * 8u;
+    uint32_t e[5], o[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 5u; ++k) e[k] = ws == 0u ? w[k] : ws == 1u ? w[k + 1] : ws == 2u ? w[k + 2] : w[k + 3];     // (constant indices: registers)
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        o[k] = (uint32_t)((((uint64_t)e[k + 1] << 32) | e[k]) >> bs);
+        const uint32_t keep = valid > 4u * k ? valid - 4u * k : 0u;   // bytes of this dword below `valid`
+        if (keep < 4u) o[k] &= keep ? (1u << (8u * keep)) - 1u : 0u;
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+__device__ __forceinline__ void lz_block_to_lds_any(uint8_t *s_dst, const uint8_t *__restrict__ src, uint32_t n, uint32_t tid)
+{
+    constexpr uint32_t NIT = (LZ_MAX_BLOCK + LZ_TAIL + 1024u * 16u - 1u) / (1024u * 16u);
+    const uint32_t sh = (uint32_t)((uintptr_t)src & 15u);
+    const uint32_t last = n ? (n - 1u) & ~15u : 0u;                   // offset of the last piece that holds a byte of the block
+    LzVec2 v[NIT];
+    if (n) {
+#pragma unroll
+        for (uint32_t k = 0; k < NIT; ++k) {
+            const uint32_t i = tid * 16u + k * 1024u * 16u;
+            v[k] = lz_load16_pair(src, n, i <= last ? i : last);
+        }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < NIT; ++k) {
+        const uint32_t i = tid * 16u + k * 1024u * 16u;
+        if (i >= LZ_MAX_BLOCK + LZ_TAIL) continue;
+        if (i >= n) *reinterpret_cast<uint4 *>(s_dst + i) = make_uint4(0u, 0u, 0u, 0u);
+        else *reinterpret_cast<uint4 *>(s_dst + i) = lz_shift16(v[k], sh, (n - i) < 16u ? (n - i) : 16u);
+    }
+}
+// the 64 bytes src[p0, p0 + 64) of such a block (p0 a multiple of 64 below n; bytes at or past n zero) as four 16-byte words
+__device__ __forceinline__ void lz_chunk64_any(const uint8_t *__restrict__ src, uint32_t n, uint32_t p0, uint4 (&v4)[4])
+{
+    const uint32_t sh = (uint32_t)((uintptr_t)src & 15u), last = (n - 1u) & ~15u;
+    LzVec2 v[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) { const uint32_t i = p0 + 16u * k; v[k] = lz_load16_pair(src, n, i <= last ? i : last); }
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t i = p0 + 16u * k;
+        v4[k] = lz_shift16(v[k], sh, i >= n ? 0u : (n - i) < 16u ? (n - i) : 16u);
+    }
+}
+template <bool DESC>
+__device__ __forceinline__ void lz_block_to_lds_of(uint8_t *s_dst, const uint8_t *__restrict__ src, uint32_t n, uint32_t tid)
+{
+    if constexpr (DESC) lz_block_to_lds_any(s_dst, src, n, tid);
+    else lz_block_to_lds(s_dst, src, n, tid);
 }
 
 // DPP moves within the wave: a lane whose source lies outside the row / wave (or in a row the row mask leaves out) keeps

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 
+template <bool DESC>                                 // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
 __global__ __launch_bounds__(1024)
 void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, LzScratch sc, Lz2Scratch s2, int use_v2,
                      uint64_t block0, uint32_t *__restrict__ trec_all)
@@ -38,14 +39,13 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     const uint32_t lb = blockIdx.x;
     long long tk = clock64();
 #define PE_TICK(k) do { if (s2.dbg && tid == 0) { long long t2 = clock64(); atomicAdd((unsigned long long *)&s2.dbg[16 + (k)], (unsigned long long)(t2 - tk)); tk = t2; } } while (0)
-    const uint64_t off = (block0 + lb) * (uint64_t)P.block;
-    const uint32_t n = (uint32_t)((n_total - off) < P.block ? (n_total - off) : P.block);
-    const uint8_t *src = in + off;
+    const uint8_t *src; uint32_t n;
+    lz_block_src<DESC>(in, n_total, P.block, block0, lb, src, n);
     const uint16_t *cand = sc.cand + (size_t)lb * LZ_MAX_BLOCK;
     const uint32_t W = 1u << P.wbits, max_len = (1u << P.lbits) - 1u;
 
     // ---- block -> LDS with the zero tail
-    lz_block_to_lds(s_r0, src, n, (uint32_t)tid);
+    lz_block_to_lds_of<DESC>(s_r0, src, n, (uint32_t)tid);
     if (tid == 0) s_L[LZ_MAX_BLOCK - 1] = 0;     // position 0xFFFF: its "pending" marker equals "none" (lz2.h); none unless a list says otherwise
     __syncthreads();
 
@@ -302,10 +302,11 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
             const uint64_t lit = my_tok & ~my_mat;
             const uint32_t p0 = (uint32_t)tid * 64u;
             if (lit) {
-                const bool v16 = (((uintptr_t)src) & 15u) == 0 && p0 + 64u <= n;
+                bool v16 = (((uintptr_t)src) & 15u) == 0 && p0 + 64u <= n;
                 // (the chunk's four 16-byte loads first, then their uses: one round trip, not four)
                 uint4 v4[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-                if (v16) {
+                if constexpr (DESC) { lz_chunk64_any(src, n, p0, v4); v16 = true; }
+                else if (v16) {
 #pragma unroll
                     for (uint32_t k4 = 0; k4 < 4u; ++k4) v4[k4] = *reinterpret_cast<const uint4 *>(src + p0 + 16u * k4);
                 }
@@ -363,9 +364,10 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
         const uint64_t lit = my_tok & ~my_mat;
         const uint32_t p0 = (uint32_t)tid * 64u;
         if (lit) {
-            const bool v16 = (((uintptr_t)src) & 15u) == 0 && p0 + 64u <= n;
+            bool v16 = (((uintptr_t)src) & 15u) == 0 && p0 + 64u <= n;
             uint4 v4[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-            if (v16) {
+            if constexpr (DESC) { lz_chunk64_any(src, n, p0, v4); v16 = true; }
+            else if (v16) {
 #pragma unroll
                 for (uint32_t k4 = 0; k4 < 4u; ++k4) v4[k4] = *reinterpret_cast<const uint4 *>(src + p0 + 16u * k4);
             }
@@ -526,20 +528,24 @@ __device__ __forceinline__ uint32_t stream_bits(const uint8_t *s, uint64_t nbyte
 // lengths and records are whole dwords, so the scan runs BEFORE the pack and the pack writes every record where it belongs:
 // no slot, no k_lz_concat, the compressed bytes cross HBM once.  mode_h = 2 (z != nullptr): the same tokens as standard
 // DEFLATE records (defz.hip), byte aligned, through slot / scan / concatenate behind the container header; the caller has
-// checked the parameters and the capacity.
-static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
-                                uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, int mode_h,
-                                const DefzCall *z = nullptr)
+// checked the parameters and the capacity.  z->batch (deflate_batch.hip): mode Z over a batch of independent items — the blocks
+// come from a descriptor table built on the device (d_in, n, d_out, cap_bytes and d_block_bits are not used; nblocks is the
+// caller's bound), and stage C places every record in its own item's buffer instead of scan / concatenate.
+mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
+                         uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, int mode_h,
+                         const DefzCall *z)
 {
-    if (!ctx || !d_out || !d_block_bits || (n && !d_in)) return MI_ERR_ARG;
+    const DfbCall *const dfb = z ? z->batch : nullptr;      // a batch of independent items
+    if (!ctx || (!dfb && (!d_out || !d_block_bits || (n && !d_in)))) return MI_ERR_ARG;
     mi_status st = lz_check_params(p);
     if (st) return st;
-    if (((uintptr_t)d_out & 3u) != 0) return MI_ERR_ARG;
+    if (!dfb && ((uintptr_t)d_out & 3u) != 0) return MI_ERR_ARG;
     if (mode_h == 1 && (!p->deflate || p->lbits > 5 || p->wbits > 16)) return MI_ERR_ARG;
     if (mode_h != 2 && cap_bytes < (mode_h ? mi_deflate_h_bound_bytes(n, p) : mi_lz_bound_bytes(n, p))) return MI_ERR_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
-    const LzP P = lz_params_of(ctx, p);
-    const uint64_t nblocks = (n + P.block - 1) / P.block;
+    LzP P = lz_params_of(ctx, p);
+    if (dfb) P.flags |= LZP_DESC;
+    const uint64_t nblocks = dfb ? dfb->max_blocks : (n + P.block - 1) / P.block;
     if (P.block > LZ_MAX_BLOCK) {
         // blocks above 64 KiB (lz77 flavour): the HBM-resident finder of lzw.hip, one stream, batches sized by workspace
         if (mode_h) return MI_ERR_ARG;
@@ -578,7 +584,7 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
     const int nsets = overlap ? MI_SETS : 1;
     const size_t set_bytes = mi_align_up(lz_scratch_bytes(nbmax), 4096);
     const size_t trec_bytes = mode_h ? (size_t)nbmax * LZ_MAX_BLOCK * 4 : 0;       // token records, one array per set
-    const size_t z_bytes = z ? defz_ws_bytes() : 0;                                  // mode Z: the checksum's partials
+    const size_t z_bytes = dfb ? dfb_ws_bytes(*dfb) : z ? defz_ws_bytes() : 0;  // mode Z: the checksum's partials; a batch: its tables
     st = mi_ws_reserve(ctx, set_bytes * nsets + 8192 + trec_bytes * nsets + z_bytes);
     if (st) return st;
     LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS];
@@ -586,7 +592,11 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
     uint64_t *base_bits = reinterpret_cast<uint64_t *>((uint8_t *)ctx->ws + set_bytes * nsets);
     uint32_t *trec_base = reinterpret_cast<uint32_t *>((uint8_t *)ctx->ws + set_bytes * nsets + 8192);
     void *zws = (uint8_t *)ctx->ws + set_bytes * nsets + 8192 + trec_bytes * nsets;
-    if (z) {
+    if (dfb) {
+        st = dfb_begin(ctx, *dfb, P.block, zws, s, &d_in);                         // (d_in: the descriptor table from here on)
+        if (st) return st;
+        if (nblocks == 0) return dfb_end(ctx, *dfb, P.block, zws, s);
+    } else if (z) {
         st = defz_begin(ctx, z->container, d_in, n, d_out, base_bits, zws, s);       // (the base starts at the header's bits)
         if (st) return st;
         if (nblocks == 0 && z->bgzf) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return bgzf_end(ctx, d_out, d_block_bits, 0, z->d_out_bytes, s); }
@@ -596,12 +606,14 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
     hipStream_t sb = overlap ? ctx->side : s, sp = overlap ? ctx->parse : s;
     // stage C of one batch (set k): parse / emit, then scan / concatenate (mode T; mode Z behind its entropy stage) or
     // mode H's entropy stage with the scan inside it, then the base moves on
+    uint64_t placed = 0;                                           // batches handed to dfb_launch_place so far
     auto stage_c = [&](int k, uint64_t b0, uint32_t nb) -> mi_status {
         uint64_t *excl_local = sc[k].block_bits;                   // reused in place by the scan
         uint32_t *trec = mode_h ? trec_base + (size_t)k * nbmax * LZ_MAX_BLOCK : nullptr;
         {
             mi_prof_scope pr(ctx, "k_lz_parse_emit", sp, (uint64_t)nb * P.block);
-            hipLaunchKernelGGL(k_lz_parse_emit, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
+            if (dfb) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
+            else hipLaunchKernelGGL(k_lz_parse_emit<false>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
         }
         if (mode_h == 1) {
             mi_prof_scope ph(ctx, "k_defh_encode", sp, (uint64_t)nb * P.block);
@@ -609,7 +621,15 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
         } else if (mode_h == 2) {
             {
                 mi_prof_scope ph(ctx, "k_defz_encode", sp, (uint64_t)nb * P.block);
-                defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp);
+                defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, dfb != nullptr, sp);
+            }
+            if (dfb) {
+                // every record to its own item (batches reach this stream in order: the item that straddles two of them goes on
+                // where the one before stopped)
+                mi_prof_scope pl(ctx, "k_dfb_place", sp, (uint64_t)nb * P.block);
+                dfb_launch_place(*dfb, zws, sc[k].slot, sc[k].block_bits, b0, nb, placed++, sp);
+                if (overlap) MI_HIP(ctx, hipEventRecord(ctx->ev_done[k], sp));
+                return MI_OK;
             }
             if (z->bgzf) {
                 mi_prof_scope pf(ctx, "k_bgzf_frame", sp, (uint64_t)nb * P.block);
@@ -730,6 +750,7 @@ static mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_
         MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_fork, 0));
     }
     MI_HIP(ctx, hipGetLastError());
+    if (dfb) return dfb_end(ctx, *dfb, P.block, zws, s);
     if (z && z->bgzf) return bgzf_end(ctx, d_out, d_block_bits, nblocks, z->d_out_bytes, s);
     if (z) return defz_end(ctx, z->container, d_out, d_block_bits, nblocks, n, zws, z->d_out_bytes, s);
     return MI_OK;

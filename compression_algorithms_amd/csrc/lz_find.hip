@@ -34,6 +34,7 @@
 // blocks and the fallback launches use a small grid (LZ_FB_GRID workgroups).
 #define LZ_FB_GRID 128u
 #define DOM_DONE 0x80000000u                          // giant_list entry handled by k_lz_emulate_dom: k_lz_emulate_giant skips it
+template <bool DESC>
 __device__ __forceinline__ void lz_sort_home_block(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, LzScratch sc, uint64_t block0,
                                                    uint32_t lb)
 {
@@ -43,13 +44,12 @@ __device__ __forceinline__ void lz_sort_home_block(const uint8_t *__restrict__ i
     __shared__ uint32_t s_u32[18];
 
     const int tid = threadIdx.x;
-    const uint64_t off = (block0 + lb) * (uint64_t)P.block;
-    const uint32_t n = (uint32_t)((n_total - off) < P.block ? (n_total - off) : P.block);
-    const uint8_t *src = in + off;
+    const uint8_t *src; uint32_t n;
+    lz_block_src<DESC>(in, n_total, P.block, block0, lb, src, n);
     const uint32_t T = 1u << P.tbits, Tmask = T - 1u;
 
     // ---- block -> LDS, zero tail (the reference reads past `size`; the parity definition is zeros)
-    lz_block_to_lds(s_in, src, n, (uint32_t)tid);
+    lz_block_to_lds_of<DESC>(s_in, src, n, (uint32_t)tid);
     if (tid < 16) s_in[LZ_MAX_BLOCK + LZ_TAIL + tid] = 0;
     __syncthreads();
 
@@ -195,6 +195,7 @@ __device__ __forceinline__ void lz_sort_home_block(const uint8_t *__restrict__ i
     }
 }
 
+template <bool DESC>
 __global__ __launch_bounds__(1024)
 void k_lz_sort_home(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, LzScratch sc, uint64_t block0, uint32_t nb,
                     const uint32_t *__restrict__ blist, const uint32_t *__restrict__ bcount)
@@ -205,7 +206,7 @@ void k_lz_sort_home(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, LzS
     // call reads is what an earlier call left (lz_emit.hip)
     if (bcount && blockIdx.x == 0 && threadIdx.x == 0 && P.order_flag) { P.order_flag[1] = count; P.order_flag[2] = nb; }
     for (uint32_t bi = blockIdx.x; bi < count; bi += gridDim.x) {
-        lz_sort_home_block(in, n_total, P, sc, block0, blist ? blist[bi] : bi);
+        lz_sort_home_block<DESC>(in, n_total, P, sc, block0, blist ? blist[bi] : bi);
         __syncthreads();
     }
 }
@@ -875,7 +876,8 @@ mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t
     const uint32_t fgrid = (blist && nb > fb_want) ? fb_want : nb;
     {
         mi_prof_scope p(ctx, "k_lz_sort_home", s, (uint64_t)nb * P.block);
-        hipLaunchKernelGGL(k_lz_sort_home, dim3(fgrid), dim3(1024), 0, s, d_in, n, P, sc, block0, nb, blist, bcount);
+        if (P.flags & LZP_DESC) hipLaunchKernelGGL(k_lz_sort_home<true>, dim3(fgrid), dim3(1024), 0, s, d_in, n, P, sc, block0, nb, blist, bcount);
+        else hipLaunchKernelGGL(k_lz_sort_home<false>, dim3(fgrid), dim3(1024), 0, s, d_in, n, P, sc, block0, nb, blist, bcount);
     }
     {
         mi_prof_scope p(ctx, "k_lz_sort_cluster", s, (uint64_t)nb * P.block);

@@ -684,3 +684,88 @@ def inflate_batch_host(items, container="gzip", ctx=None, verify=True):
     st = ctx.L.mi_inflate_batch(ctx.h, c, count, h_in, h_nb, h_out, h_cap, sizes, status, flags)
     _lib.check(st, "mi_inflate_batch")
     return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]
+
+
+# ---- batched deflate: many independent buffers, each a complete raw / zlib / gzip stream, in one call (include/mi_codec.h) ------
+class DeflateBatch(InflateBatch):
+    """The result of deflate_batch, shaped like InflateBatch: `outputs` (a list of uint8 device tensors, each cut to its stream;
+    empty where the item failed), `out_bytes` (int64; the size needed where the status is MI_ERR_CAPACITY) and `status` (int32)
+    device tensors, `failed` (how many items are not MI_OK)."""
+
+    def raise_for_status(self):
+        if self.failed:
+            st = [int(v) for v in self.status.cpu()]
+            i = next(k for k, v in enumerate(st) if v)
+            raise _lib.MiError(st[i], f"deflate_batch: {self.failed} of {len(st)} items failed, the first one item {i}")
+        return self
+
+
+def deflate_batch_max_blocks(total_bytes, count, p=None):
+    """mi_deflate_batch_max_blocks: an upper bound on the blocks of `count` items of `total_bytes` together"""
+    p = p or params("deflate")
+    return int(_lib.lib().mi_deflate_batch_max_blocks(total_bytes, count, C.byref(p)))
+
+
+def deflate_batch(items, p=None, container="gzip", caps=None, ctx=None, max_blocks=None):
+    """Compress many independent buffers in one call -> DeflateBatch.  Item i's stream is byte for byte compress_z(item i).
+
+    items: a list of bytes or uint8 tensors, or a pair (buffer, offsets) for a packed buffer with count + 1 offsets (item i
+    is buffer[offsets[i]:offsets[i + 1]]: no alignment needed), as for inflate_batch.  caps: the output capacity of every
+    item (list or tensor); None gives each item its bound in one packed output.  An item that does not fit its capacity
+    comes back MI_ERR_CAPACITY with out_bytes = the size it needs; one bad item does not spoil the rest.  max_blocks: the
+    launch bound (None: from the sizes, which are known here)."""
+    off, count = _batch_check(items, caps)
+    c = CONTAINERS.get(container, container)
+    if c not in CONTAINERS.values():
+        raise ValueError(f"container {container!r}: one of {sorted(CONTAINERS)}")
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    sizes = [int(v) for v in d_nb.cpu()] if count else []
+    if caps is None:
+        cap = [bound_bytes_z(n, p, c) for n in sizes]
+    else:
+        cap = [int(v) for v in (caps.cpu().tolist() if torch.is_tensor(caps) else caps)]
+    d_cap = torch.tensor(cap, dtype=torch.int64, device=ctx.device) if count else torch.zeros(0, dtype=torch.int64, device=ctx.device)
+    at, offs = 0, []
+    for v in cap:
+        offs.append(at)
+        at += (min(v, 0x7FFFFFFF) + 15) & ~15                 # (a capacity above that is refused per item)
+    out = torch.empty(max(at, 16), dtype=torch.uint8, device=ctx.device)
+    d_out = torch.tensor([out.data_ptr() + a for a in offs], dtype=torch.int64, device=ctx.device) if count else d_cap
+    if max_blocks is None:
+        max_blocks = sum((n + p.block - 1) // p.block for n in sizes if n <= 0x7FFFFFFF)
+    nbytes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+    v0 = ctx.order_violations()
+    st = ctx.L.mi_deflate_batch_dev(ctx.h, C.byref(p), c, count, _ptr(d_in), _ptr(d_nb), max_blocks, _ptr(d_out), _ptr(d_cap),
+                                    _ptr(nbytes), _ptr(status), _ptr(failed), ctx.stream_ptr())
+    _lib.check(st, "mi_deflate_batch_dev")
+    ctx.sync()
+    if ctx.order_violations() != v0:
+        raise _lib.MiError(10, "the encoder that wrote this batch reported a sort out of order")
+    nb, stl = [int(v) for v in nbytes[:count].cpu()], [int(v) for v in status[:count].cpu()]
+    outputs = [out[a:a + (n if s == 0 else 0)] for a, n, s in zip(offs, nb, stl)]
+    return DeflateBatch(outputs, nbytes[:count], status[:count], int(failed.item()) if count else 0)
+
+
+def deflate_batch_host(items, p=None, container="gzip", ctx=None):
+    """the host-buffer entry point (mi_deflate_batch): a list of bytes -> (list of bytes, None where the item failed; list of
+    status codes)"""
+    items = [bytes(x) for x in items]
+    count = len(items)
+    c = CONTAINERS.get(container, container)
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    arrs = [np.frombuffer(b, dtype=np.uint8) for b in items]
+    h_in = (C.c_void_p * max(count, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    h_nb = (C.c_uint64 * max(count, 1))(*[a.size for a in arrs])
+    caps = [bound_bytes_z(a.size, p, c) for a in arrs]
+    outs = [np.zeros(max(v, 1), dtype=np.uint8) for v in caps]
+    h_out = (C.c_void_p * max(count, 1))(*[o.ctypes.data for o in outs])
+    h_cap = (C.c_uint64 * max(count, 1))(*caps)
+    sizes, status = (C.c_uint64 * max(count, 1))(), (C.c_uint32 * max(count, 1))()
+    st = ctx.L.mi_deflate_batch(ctx.h, C.byref(p), c, count, h_in, h_nb, h_out, h_cap, sizes, status)
+    _lib.check(st, "mi_deflate_batch")
+    return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]

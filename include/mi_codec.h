@@ -536,6 +536,52 @@ mi_status mi_inflate_batch(mi_ctx *ctx, uint32_t container, uint64_t count, cons
                            void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status, uint32_t flags);
 
 /* ------------------------------------------------------------------------------------
+ * Batched deflate: many independent buffers compressed in ONE call, each from its own address
+ * and of its own size into its own buffer as a complete raw, zlib or gzip stream (one container
+ * per call) — the twin of the batched inflate above, for Parquet / ORC pages, zarr / HDF5 chunks,
+ * PNG IDAT, HTTP bodies.  The blocks of all items run through the one mode-Z pipeline, and item
+ * i's output is byte for byte what mi_deflate_z_encode_dev writes for item i alone (same p, same
+ * container): one record per p->block input bytes, then 03 00 and the trailer.
+ * All arrays are DEVICE arrays of `count` entries.  p: as mode Z (the deflate flavour, wbits <= 15,
+ * lbits <= 8, block <= 65536).  No alignment is required of d_in[i] or d_out[i].  Reads stay
+ * inside the item's own bytes, rounded out to whole aligned 16-byte words; writes inside
+ * [d_out[i], d_out[i] + d_out_cap[i]).  Items may overlap in their inputs but not in their
+ * outputs.  An item never influences another item's bytes or verdict.
+ * max_blocks: a HOST-side upper bound on the sum of ceil(d_in_bytes[i] / p->block), so that grids
+ * and workspace are sized without reading the device; the batch max_blocks helper below gives it
+ * from a bound on the total bytes (total / block + count).  Every block of the bound costs a
+ * workgroup per stage whether an item fills it or not: keep it tight.  If the device finds more
+ * blocks than the bound, the items whose blocks do not fit — the first such item and every item
+ * behind it — are MI_ERR_ARG; the items before them are unaffected.
+ *
+ * Per item, on the device: d_status[i] (an mi_status) and d_out_bytes[i] —
+ *   MI_OK            d_out_bytes[i] = the stream's size, <= d_out_cap[i].  An empty item is MI_OK:
+ *                    the container header, 03 00 and the trailer, as mode Z writes for n = 0.
+ *   MI_ERR_CAPACITY  d_out_bytes[i] = the exact size the caller must provide (at most the batch
+ *                    bound of the item's size).  Nothing is written at or past the capacity; the
+ *                    bytes below it are unspecified.
+ *   MI_ERR_ARG       d_out_bytes[i] = 0: a NULL pointer with a non-zero size or capacity;
+ *                    d_in_bytes[i] or d_out_cap[i] above 2^31 - 1; blocks beyond max_blocks.
+ * *d_failed (may be NULL) = the number of items whose status is not MI_OK.
+ * The call itself returns only MI_OK, MI_ERR_ARG (NULL arrays, p or a container mode Z refuses,
+ * count or max_blocks above 2^31 - 1), MI_ERR_HIP or MI_ERR_NOMEM; count == 0 is MI_OK and
+ * launches nothing.  Asynchronous on `stream` under the encoders' contract (top of file): no host
+ * synchronisation and no device-to-host read; read the verdicts after mi_sync or in stream order.
+ * MI_LZ_BATCH (blocks per pipeline batch) works as in every encoder; an item's blocks may
+ * straddle pipeline batches.
+ * The host form: arrays of host pointers — copy up, encode, copy down the items that came out MI_OK.
+ * ------------------------------------------------------------------------------------ */
+uint64_t  mi_deflate_batch_bound_bytes(uint64_t n_item, const mi_lz_params *p, uint32_t container);   /* = mi_deflate_z_bound_bytes */
+uint64_t  mi_deflate_batch_max_blocks(uint64_t total_in_bytes, uint64_t count, const mi_lz_params *p); /* total / block + count */
+mi_status mi_deflate_batch_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
+                               const void *const *d_in, const uint64_t *d_in_bytes, uint64_t max_blocks,
+                               void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                               uint32_t *d_status, uint32_t *d_failed, void *stream);
+mi_status mi_deflate_batch(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
+                           const void *const *h_in, const uint64_t *h_in_bytes,
+                           void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status);
+
+/* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is
  * defined by this build).  Record layout in include/mi_fse.h.
  * ------------------------------------------------------------------------------------ */
