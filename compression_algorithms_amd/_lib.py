@@ -62,6 +62,7 @@ EXPORTS = [
     "mi_inflate_batch_dev", "mi_inflate_batch_size_dev", "mi_inflate_batch",
     "mi_deflate_batch_bound_bytes", "mi_deflate_batch_max_blocks", "mi_deflate_batch_dev", "mi_deflate_batch",
     "mi_bgzf_bound_bytes", "mi_bgzf_encode_dev", "mi_bgzf_encode", "mi_bgzf_index_dev", "mi_bgzf_inflate_dev", "mi_bgzf_inflate",
+    "mi_bgzf_read_max_pieces", "mi_bgzf_read_ranges_dev", "mi_bgzf_read_ranges",
     "mi_fse_block_bound", "mi_fse_encode_dev", "mi_fse_decode_dev", "mi_fse_encode", "mi_fse_decode", "mi_fse_normalise_dev",
     "mi_set_profiling", "mi_get_kernel_times",
     "mi_multi_create", "mi_multi_destroy", "mi_multi_ndev", "mi_multi_ctx", "mi_multi_transport", "mi_multi_last_transport_error",
@@ -168,6 +169,12 @@ def lib():
             L.mi_bgzf_index_dev.argtypes = [vp, vp, u64, vp, u64, vp, vp]
             L.mi_bgzf_inflate_dev.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, u32, vp]
             L.mi_bgzf_inflate.argtypes = [vp, vp, u64, vp, u64, vp, u32]
+        if hasattr(L, "mi_bgzf_read_ranges_dev"):
+            u32 = C.c_uint32
+            L.mi_bgzf_read_max_pieces.restype = u64
+            L.mi_bgzf_read_max_pieces.argtypes = [u64, u64, u64]
+            L.mi_bgzf_read_ranges_dev.argtypes = [vp, vp, u64, vp, u64, u64, vp, vp, vp, vp, u64, u64, vp, vp, vp, u32, vp]
+            L.mi_bgzf_read_ranges.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp, u32]
         if hasattr(L, "mi_fse_encode_dev"):
             L.mi_fse_block_bound.restype = u64
             L.mi_fse_block_bound.argtypes = [C.POINTER(FseParams)]

@@ -22,6 +22,7 @@
 #include "lz_common.h"
 #include "crc32.h"
 #include "internal.h"
+#include "bgzf_core.h"                 // the member header and its check against a table, shared with bgzf_ranges.hip
 
 // a member of the largest block in its stored form: header 18, record b + 5 ceil(b / 65535) + 5, 03 00, trailer 8
 static_assert(MI_BGZF_MAX_BLOCK + 5u * ((MI_BGZF_MAX_BLOCK + 65534u) / 65535u) + 5u + 2u + 26u <= 65536u, "BSIZE fits 16 bits");
@@ -30,7 +31,6 @@ static_assert(MI_BGZF_BLOCK <= MI_BGZF_MAX_BLOCK && 65536u / 4u + 8u < LZ_SLOT_W
 
 #define BGZF_HDR       18u                     // 1F 8B 08 04 MTIME(4) XFL OS XLEN(2) 'B' 'C' 02 00 BSIZE(2)
 #define BGZF_FRAME     28u                     // header + 03 00 + CRC-32 + ISIZE
-#define BGZF_MIN       28u                     // the shortest member an index accepts: 12 + XLEN (>= 6) + 2 + 8
 #define BGZF_CHUNK     131072ull               // index: stream bytes per wave; > 65 536, so every chunk but the last holds a member start
 #define BGZF_TRIES     8u                      // guessed entries tried per chunk before it is left to the verify pass
 #define BGZF_NONE      (~0ull)
@@ -163,33 +163,7 @@ extern "C" mi_status mi_bgzf_encode(mi_ctx *ctx, const mi_lz_params *p, const ui
 // ---------------------------------------------------------------------------------------------
 // read: the member header
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t bgzf_le16(const uint8_t *s, uint64_t i) { return (uint32_t)s[i] | ((uint32_t)s[i + 1] << 8); }
-__device__ __forceinline__ uint32_t bgzf_le32(const uint8_t *s, uint64_t i) { return bgzf_le16(s, i) | (bgzf_le16(s, i + 2) << 16); }
-
-// The member that starts at `pos` and must lie inside [pos, end), end <= the stream's length: nothing outside that range is
-// read.  RFC 1952 header with CM = 8 and FLG = FEXTRA alone; the subfields of the XLEN bytes in turn, the first 'B' 'C' of
-// length 2 that lies inside them gives BSIZE (a subfield that runs past XLEN ends the search); the member's BSIZE + 1 bytes
-// hold at least the header, an empty DEFLATE stream and the trailer; ISIZE, its last four bytes, is at most 65 536.
-__device__ bool bgzf_parse(const uint8_t *__restrict__ s, uint64_t pos, uint64_t end, uint32_t &msize, uint32_t &isize, uint32_t &xlen)
-{
-    if (end < pos || end - pos < BGZF_MIN) return false;
-    if (s[pos] != 0x1Fu || s[pos + 1] != 0x8Bu || s[pos + 2] != 8u || s[pos + 3] != 4u) return false;
-    xlen = bgzf_le16(s, pos + 10);
-    if (12ull + xlen + 2u + 8u > end - pos) return false;
-    bool found = false;
-    uint32_t bsize = 0;
-    for (uint32_t q = 0; q + 4u <= xlen && !found;) {                  // every round moves on by at least 4 of <= 65 535 bytes
-        const uint64_t f = pos + 12u + q;
-        const uint32_t slen = bgzf_le16(s, f + 2);
-        if (s[f] == 0x42u && s[f + 1] == 0x43u && slen == 2u && q + 6u <= xlen) { bsize = bgzf_le16(s, f + 4); found = true; }
-        q += 4u + slen;
-    }
-    if (!found) return false;
-    msize = bsize + 1u;
-    if (msize < xlen + 12u + 2u + 8u || msize > end - pos) return false;
-    isize = bgzf_le32(s, pos + msize - 4u);
-    return isize <= 65536u;
-}
+// (bgzf_parse, the member header as include/mi_codec.h reads it: bgzf_core.h)
 
 // Members from `pos` while they start before `lim` (<= nbytes); false where one does not parse.  Every lane of the wave
 // runs it with the same arguments.  put(k, stream offset, output bytes before it) sees every member.
@@ -377,27 +351,35 @@ void k_bgzf_segments(const uint8_t *__restrict__ s, uint64_t nbytes, const uint6
     const uint64_t s0 = members[2u * m], o0 = members[2u * m + 1u], s1 = members[2u * m + 2u], o1 = members[2u * m + 3u];
     const uint64_t obase = members[2u * first + 1u];
     InfSeg d = {0, 0, 0, 0, 0};
-    bool ok = s0 <= s1 && s1 <= nbytes && s1 - s0 <= 65536u && o0 >= obase && o1 >= o0 && o1 - o0 <= 65536u && o1 - obase <= out_bytes;
+    bool ok = o0 >= obase && o1 >= o0 && o1 - obase <= out_bytes;
     if (ok && i + 1u == nmem) ok = o1 - obase == out_bytes;            // the range fills the output exactly
-    uint32_t msize = 0, isize = 0, xlen = 0;
-    ok = ok && bgzf_parse(s, s0, s1, msize, isize, xlen) && msize == s1 - s0 && isize == o1 - o0;
-    if (ok) {
-        d.first_bit = 8u * (s0 + 12u + xlen); d.last_bit = 8u * (s1 - 8u);
-        d.out_off = o0 - obase; d.out_len = isize; d.crc = bgzf_le32(s, s1 - 8u);
-    } else atomicOr(err, 1u);
+    ok = ok && bgzf_member_seg(s, nbytes, s0, o0, s1, o1, d);          // (bgzf_core.h: the table's pairs and the header read again)
+    if (ok) d.out_off = o0 - obase;
+    else atomicOr(err, 1u);                                            // (d is still all zero)
     seg[i] = d;
 }
 
+// seg_status (bgzf_ranges.hip; NULL: the one `err` word): a segment whose word is not zero is not read at all, and a
+// mismatch sets the segment's own word
 __global__ __launch_bounds__(ZCK_THREADS)
-void k_bgzf_check(const uint8_t *__restrict__ out, const InfSeg *__restrict__ seg, uint32_t *__restrict__ err)
+void k_bgzf_check(const uint8_t *__restrict__ out, const InfSeg *__restrict__ seg, uint32_t *__restrict__ err, uint32_t *__restrict__ seg_status)
 {
     __shared__ CrcLds s_crc;
     const uint32_t tid = threadIdx.x;
+    if (seg_status && seg_status[blockIdx.x] != 0u) return;            // (the whole workgroup)
     const InfSeg d = seg[blockIdx.x];
     crc_lds_init(s_crc, tid);
     __syncthreads();
     const uint32_t pure = crc_range(out + d.out_off, d.out_len, s_crc, tid);
-    if (tid == 0 && crc_standard(pure, d.out_len) != d.crc) atomicOr(err, 1u);
+    if (tid == 0 && crc_standard(pure, d.out_len) != d.crc) {
+        if (seg_status) seg_status[blockIdx.x] = 1u;
+        else atomicOr(err, 1u);
+    }
+}
+
+void bgzf_launch_check(const uint8_t *d_out, const InfSeg *d_seg, uint32_t nseg, uint32_t *err, hipStream_t s, uint32_t *seg_status)
+{
+    hipLaunchKernelGGL(k_bgzf_check, dim3(nseg), dim3(ZCK_THREADS), 0, s, d_out, d_seg, err, seg_status);
 }
 
 extern "C" mi_status mi_bgzf_inflate_dev(mi_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_members,
@@ -423,7 +405,7 @@ extern "C" mi_status mi_bgzf_inflate_dev(mi_ctx *ctx, const uint8_t *d_stream, u
     }
     if (!(flags & MI_INFLATE_NO_CHECKSUM)) {
         mi_prof_scope pr(ctx, "k_bgzf_check", s, out_bytes);
-        hipLaunchKernelGGL(k_bgzf_check, dim3(nmem), dim3(ZCK_THREADS), 0, s, d_out, seg, err);
+        bgzf_launch_check(d_out, seg, nmem, err, s);
     }
     if (hipGetLastError() != hipSuccess) return MI_ERR_HIP;
     uint32_t h_err = 0;

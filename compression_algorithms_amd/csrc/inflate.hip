@@ -33,11 +33,14 @@
 
 // DESC (BGZF, bgzf.hip): `seg_bits` points at one InfSeg descriptor per segment instead of the table — the segment's first
 // and last bit, output offset and output length; block, nseg and n_total are not used.  Every segment is a whole DEFLATE
-// stream then: its last block, and only that one, has BFINAL = 1.
+// stream then: its last block, and only that one, has BFINAL = 1.  seg_status (DESC only, may be NULL; bgzf_ranges.hip): one
+// word per segment instead of the one `err` word — a segment whose word is not zero on entry is not decoded at all, and a
+// segment that fails sets its own word to 1, so that no verdict reaches another segment's owner.
 template <uint32_t RING, bool DESC = false>
 __global__ __launch_bounds__(64)
 void k_inflate(const uint8_t *__restrict__ stream, uint64_t stream_bytes, const uint64_t *__restrict__ seg_bits, uint32_t block,
-               uint64_t nseg, uint8_t *__restrict__ out, uint64_t n_total, uint32_t *__restrict__ status, uint32_t *__restrict__ err)
+               uint64_t nseg, uint8_t *__restrict__ out, uint64_t n_total, uint32_t *__restrict__ status, uint32_t *__restrict__ err,
+               uint32_t *__restrict__ seg_status)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_ring[RING];
     __shared__ uint16_t s_llut[1 << INF_LL_BITS], s_dlut[1 << INF_D_BITS];     // symbol | length << 9
@@ -46,6 +49,8 @@ void k_inflate(const uint8_t *__restrict__ stream, uint64_t stream_bytes, const 
     __shared__ __attribute__((aligned(4))) uint8_t s_len[288 + 32 + 4], s_cl[20];
     const uint32_t lane = threadIdx.x;
     const uint64_t sg = blockIdx.x;
+    if (DESC && seg_status && seg_status[sg] != 0u) return;            // (the whole wave: inert or refused before it got here)
+    auto fail = [&]() { if (lane == 0) { if (DESC && seg_status) seg_status[sg] = 1u; else atomicOr(err, 1u); } };
     InfSeg d = {};
     if constexpr (DESC) d = reinterpret_cast<const InfSeg *>(seg_bits)[sg];
     const uint64_t off = DESC ? d.out_off : sg * (uint64_t)block;
@@ -53,7 +58,7 @@ void k_inflate(const uint8_t *__restrict__ stream, uint64_t stream_bytes, const 
     const uint64_t rb = DESC ? d.first_bit : seg_bits[sg], re = DESC ? d.last_bit : seg_bits[sg + 1];
     // the segment must lie inside the stream, on byte boundaries: every later read is bounded by [rb, re)
     bool bad = ((rb | re) & 7u) || re < rb || re > stream_bytes * 8ull;
-    if (bad) { if (lane == 0) atomicOr(err, 1u); return; }
+    if (bad) { fail(); return; }
     const uint64_t nbits = re - rb;
     const bool may_end = DESC || nseg == 1u;                           // the one-segment rule: BFINAL = 1 may close the segment
 
@@ -68,18 +73,18 @@ void k_inflate(const uint8_t *__restrict__ stream, uint64_t stream_bytes, const 
     if (final_seen ? ((pos + 7u) & ~7ull) != nbits : pos != nbits) bad = true;
     if (o != n) bad = true;
     if (DESC && !final_seen) bad = true;
-    if (bad) { if (lane == 0) atomicOr(err, 1u); return; }
+    if (bad) { fail(); return; }
     ring.finish(n);
     if (!DESC && final_seen && lane == 0) status[INF_WS_FINAL] = 1u;
 }
 
 // BGZF: one wave per member descriptor (the caller has checked every descriptor against the stream and the output range)
 void inflate_launch_segments(const uint8_t *d_stream, uint64_t stream_bytes, const InfSeg *d_seg, uint32_t nseg, uint8_t *d_out,
-                             uint32_t *err, hipStream_t s)
+                             uint32_t *err, hipStream_t s, uint32_t *seg_status)
 {
     const uint64_t *desc = reinterpret_cast<const uint64_t *>(d_seg);
-    if (nseg >= 1024u) hipLaunchKernelGGL((k_inflate<4096u, true>), dim3(nseg), dim3(64), 0, s, d_stream, stream_bytes, desc, 0u, (uint64_t)nseg, d_out, (uint64_t)0, (uint32_t *)nullptr, err);
-    else hipLaunchKernelGGL((k_inflate<32768u, true>), dim3(nseg), dim3(64), 0, s, d_stream, stream_bytes, desc, 0u, (uint64_t)nseg, d_out, (uint64_t)0, (uint32_t *)nullptr, err);
+    if (nseg >= 1024u) hipLaunchKernelGGL((k_inflate<4096u, true>), dim3(nseg), dim3(64), 0, s, d_stream, stream_bytes, desc, 0u, (uint64_t)nseg, d_out, (uint64_t)0, (uint32_t *)nullptr, err, seg_status);
+    else hipLaunchKernelGGL((k_inflate<32768u, true>), dim3(nseg), dim3(64), 0, s, d_stream, stream_bytes, desc, 0u, (uint64_t)nseg, d_out, (uint64_t)0, (uint32_t *)nullptr, err, seg_status);
 }
 
 // The frame around the segments, read by one lane: bytes past the stream read as zero and count as corrupt.
@@ -155,8 +160,8 @@ extern "C" mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t bl
         // the whole 32 KiB window in LDS.
         const char *e = getenv("MI_LZ_DECODE_RING");
         const uint32_t want = e ? (uint32_t)atoi(e) : (nseg < 1024u ? 32768u : 4096u);
-        if (want <= 4096u) hipLaunchKernelGGL(k_inflate<4096u>, dim3((unsigned)nseg), dim3(64), 0, s, d_stream, stream_bytes, d_seg_bits, block, nseg, d_out, n, status, err);
-        else hipLaunchKernelGGL(k_inflate<32768u>, dim3((unsigned)nseg), dim3(64), 0, s, d_stream, stream_bytes, d_seg_bits, block, nseg, d_out, n, status, err);
+        if (want <= 4096u) hipLaunchKernelGGL(k_inflate<4096u>, dim3((unsigned)nseg), dim3(64), 0, s, d_stream, stream_bytes, d_seg_bits, block, nseg, d_out, n, status, err, (uint32_t *)nullptr);
+        else hipLaunchKernelGGL(k_inflate<32768u>, dim3((unsigned)nseg), dim3(64), 0, s, d_stream, stream_bytes, d_seg_bits, block, nseg, d_out, n, status, err, (uint32_t *)nullptr);
         if (hipGetLastError() != hipSuccess) return MI_ERR_HIP;
     }
     if (container != MI_CONTAINER_RAW && !(flags & MI_INFLATE_NO_CHECKSUM)) {

@@ -88,9 +88,14 @@ mi_status dfb_end(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipSt
 // ---- inflate.hip: k_inflate over segment descriptors (BGZF members) instead of a table of restart points
 struct InfSeg { uint64_t first_bit, last_bit, out_off; uint32_t out_len, crc; };   // crc: the member's trailer, for bgzf.hip
 void      inflate_launch_segments(const uint8_t *d_stream, uint64_t stream_bytes, const InfSeg *d_seg, uint32_t nseg, uint8_t *d_out,
-                                  uint32_t *err, hipStream_t s);
+                                  uint32_t *err, hipStream_t s, uint32_t *seg_status = nullptr);
+// seg_status: one word per segment instead of `err` (which may then be NULL) — a segment whose word is not zero is skipped, one
+// that fails sets its word to 1
 
-// ---- bgzf.hip: the member framing of one batch of mode-Z records in their slots; the EOF member and the total
+// ---- bgzf.hip: the member framing of one batch of mode-Z records in their slots; the EOF member and the total; the CRC-32 of
+// decoded members against their trailers, one workgroup per descriptor (seg_status as for inflate_launch_segments)
+void      bgzf_launch_check(const uint8_t *d_out, const InfSeg *d_seg, uint32_t nseg, uint32_t *err, hipStream_t s,
+                            uint32_t *seg_status = nullptr);
 void      bgzf_launch_frame(uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n, uint32_t block, uint64_t b0,
                             uint32_t nb, hipStream_t s);
 mi_status bgzf_end(mi_ctx *ctx, uint8_t *d_out, const uint64_t *d_member_bits, uint64_t nblocks, uint64_t *d_out_bytes, hipStream_t s);

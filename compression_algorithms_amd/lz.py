@@ -532,6 +532,149 @@ def decompress_bgzf_host(data, ctx=None, verify=True, out_cap=None):
     return out[: nb.value].tobytes()
 
 
+# ---- BGZF byte ranges: many (offset, length) slices of the uncompressed data in one call (include/mi_codec.h) ---------
+class BgzfRead(tuple):
+    """(out, out_offsets, got, status) of bgzf_read: the uint8 output, where every range's slot starts in it (int64), the
+    bytes delivered per range (int64) and the verdict per range (int32), device tensors; .failed counts the ranges that are
+    not MI_OK (reading it synchronises)."""
+
+    def __new__(cls, out, out_offsets, got, status, failed):
+        self = super().__new__(cls, (out, out_offsets, got, status))
+        self._failed = failed
+        return self
+
+    @property
+    def failed(self):
+        return int(self._failed.item())
+
+
+def _index_pairs(members, device):
+    pairs = members.pairs if isinstance(members, BgzfIndex) else torch.stack([torch.as_tensor(members[0]), torch.as_tensor(members[1])], 1)
+    return pairs.to(device=device, dtype=torch.int64).contiguous()
+
+
+def bgzf_piece_counts(out_offsets, ranges):
+    """The pieces of every range — one per non-empty member that holds a byte of it — from the members' output offsets
+    (members + 1 entries, not decreasing) -> int64 tensor [R].  Pure torch, on whatever device the offsets live."""
+    o = torch.as_tensor(out_offsets).to(torch.int64)
+    r = torch.as_tensor(ranges).to(device=o.device, dtype=torch.int64).reshape(-1, 2)
+    total = o[-1]
+    keep = o[1:] != o[:-1]
+    starts, ends = o[:-1][keep].contiguous(), o[1:][keep].contiguous()
+    a = r[:, 0].contiguous()
+    b = torch.minimum(a + r[:, 1], total)
+    k0 = torch.searchsorted(ends, a, right=True)               # the first member that ends behind a
+    k1 = torch.searchsorted(starts, b, right=False)            # the first member that starts at or behind b
+    live = (r[:, 1] > 0) & (a < total)
+    return torch.where(live, (k1 - k0).clamp(min=0), torch.zeros_like(k0))
+
+
+def bgzf_read_max_pieces(count, total_len, min_member_bytes=BGZF_BLOCK):
+    """mi_bgzf_read_max_pieces: a bound on the pieces of `count` ranges of `total_len` bytes together over members of at
+    least `min_member_bytes` uncompressed bytes (bgzip: 65 280)"""
+    return int(_lib.lib().mi_bgzf_read_max_pieces(count, total_len, min_member_bytes))
+
+
+def bgzf_voffset_to_offset(index, voffsets):
+    """htslib virtual offsets (coffset << 16 | uoffset: where the member starts in the file, and a position inside its
+    uncompressed bytes) -> offsets into the uncompressed data, by the index (a BgzfIndex, or (stream offsets, output
+    offsets)).  ValueError where coffset is not a member's start or uoffset exceeds that member's size.  Pure torch."""
+    so, oo = torch.as_tensor(index[0]).to(torch.int64), torch.as_tensor(index[1]).to(torch.int64)
+    v = torch.as_tensor(voffsets).to(device=so.device, dtype=torch.int64).reshape(-1)
+    co, uo = v >> 16, v & 0xFFFF
+    starts = so[:-1].contiguous()
+    if starts.numel() == 0:
+        if v.numel():
+            raise ValueError("the index has no members")
+        return v
+    # (empty streams aside, member starts increase strictly: a member has at least 28 bytes)
+    k = torch.searchsorted(starts, co.contiguous(), right=False).clamp(max=starts.numel() - 1)
+    if bool((starts[k] != co).any()):
+        bad = int(co[(starts[k] != co).nonzero()[0, 0]])
+        raise ValueError(f"coffset {bad} is not the start of a member")
+    size = oo[k + 1] - oo[k]
+    if bool((uo > size).any()):
+        i = int((uo > size).nonzero()[0, 0])
+        raise ValueError(f"uoffset {int(uo[i])} exceeds the {int(size[i])} bytes of the member at {int(co[i])}")
+    return oo[k] + uo
+
+
+def bgzf_read(data, ranges, members=None, verify=True, ctx=None, max_pieces=None, out=None, out_offsets=None):
+    """Many byte ranges of a BGZF stream's uncompressed data in one call -> BgzfRead, which unpacks as (out, out_offsets,
+    got, status).  ranges: [R, 2] int64 (offset, length) tensor or array, in any order, overlapping or repeated as they
+    like.  A range that ends past the end of the data is a short read (got < length, status MI_OK).  members: a BgzfIndex
+    (made here if None).  max_pieces: the launch bound (None: the exact count, by torch.searchsorted over the index — one
+    synchronisation; pass bgzf_read_max_pieces(...) to avoid it).  out / out_offsets: a uint8 device tensor to write into
+    and where each range's slot starts in it (None: a new tensor with the slots packed back to back); slots must not
+    overlap, and a slot that leaves `out` is MI_ERR_ARG for its range.  One bad range does not spoil the rest."""
+    ctx = ctx or default_context()
+    if isinstance(data, BgzfStream):
+        data = data.data[: data.nbytes]
+    if torch.is_tensor(data) and data.device == ctx.device and data.dtype == torch.uint8 and data.is_contiguous() and data.data_ptr() % 4 == 0:
+        d_stream = data                                        # (the library asks for 4-byte alignment only)
+    else:
+        d_stream = as_device_bytes(data, ctx.device)
+    if members is None:
+        members = bgzf_index(d_stream, ctx)
+    pairs = _index_pairs(members, ctx.device)
+    r = torch.as_tensor(np.asarray(ranges, dtype=np.int64) if not torch.is_tensor(ranges) else ranges)
+    r = r.to(device=ctx.device, dtype=torch.int64).reshape(-1, 2)
+    count = r.shape[0]
+    if bool((r < 0).any()) if count else False:
+        raise ValueError("offsets and lengths must not be negative")
+    d_off, d_len = r[:, 0].contiguous(), r[:, 1].contiguous()
+    if out_offsets is None:
+        d_at = torch.cumsum(d_len, 0) - d_len
+    else:
+        d_at = torch.as_tensor(out_offsets).to(device=ctx.device, dtype=torch.int64).reshape(-1).contiguous()
+        if d_at.numel() != count:
+            raise ValueError(f"out_offsets has {d_at.numel()} entries for {count} ranges")
+    if out is None:
+        need = int((d_at + d_len).max()) if count else 0
+        out = torch.empty(max(need, 1), dtype=torch.uint8, device=ctx.device)
+        out_bytes = need
+    else:
+        if not (torch.is_tensor(out) and out.device == ctx.device and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous uint8 tensor on the context's device")
+        out_bytes = out.numel()
+    if max_pieces is None:
+        max_pieces = int(bgzf_piece_counts(pairs[:, 1], r).sum()) if count else 0
+    got = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+    st = ctx.L.mi_bgzf_read_ranges_dev(ctx.h, _ptr(d_stream), d_stream.numel(), C.c_void_p(pairs.data_ptr()), pairs.shape[0] - 1, count,
+                                       _ptr(d_off), _ptr(d_len), C.c_void_p(out.data_ptr()), _ptr(d_at), out_bytes, max_pieces,
+                                       _ptr(got), _ptr(status), _ptr(failed), 0 if verify else MI_INFLATE_NO_CHECKSUM, ctx.stream_ptr())
+    _lib.check(st, "mi_bgzf_read_ranges_dev")
+    return BgzfRead(out, d_at, got[:count], status[:count], failed)
+
+
+def bgzf_read_host(data, ranges, ctx=None, verify=True, out=None, out_offsets=None):
+    """the host-buffer entry point (mi_bgzf_read_ranges: copy up, index, read, copy down) -> (out as a numpy uint8 array,
+    out_offsets, got, status as lists)"""
+    ctx = ctx or default_context()
+    buf = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+    if (r < 0).any():
+        raise ValueError("offsets and lengths must not be negative")
+    count = r.shape[0]
+    off, ln = np.ascontiguousarray(r[:, 0]).astype(np.uint64), np.ascontiguousarray(r[:, 1]).astype(np.uint64)
+    at = (np.cumsum(ln) - ln).astype(np.uint64) if out_offsets is None else np.ascontiguousarray(np.asarray(out_offsets, dtype=np.int64).reshape(-1)).astype(np.uint64)
+    if at.size != count:
+        raise ValueError(f"out_offsets has {at.size} entries for {count} ranges")
+    if out is None:
+        out_bytes = int((at + ln).max()) if count else 0
+        out = np.zeros(max(out_bytes, 1), dtype=np.uint8)
+    else:
+        out_bytes = out.size
+    got, status = np.zeros(max(count, 1), dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    st = ctx.L.mi_bgzf_read_ranges(ctx.h, vp(buf), buf.size, count, vp(off), vp(ln), vp(out), vp(at), out_bytes, vp(got), vp(status),
+                                   0 if verify else MI_INFLATE_NO_CHECKSUM)
+    _lib.check(st, "mi_bgzf_read_ranges")
+    return out, [int(v) for v in at], [int(v) for v in got[:count]], [int(v) for v in status[:count]]
+
+
 # ---- batched inflate: many independent raw / zlib / gzip streams in one launch (include/mi_codec.h) -------------------
 def _is_packed(items):
     return (isinstance(items, tuple) and len(items) == 2 and not isinstance(items[1], (bytes, bytearray, memoryview))

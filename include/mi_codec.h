@@ -24,8 +24,8 @@
  * Decoders (*_decode_dev) synchronise `stream` before returning: MI_ERR_CORRUPT is decided on the device.  They take the
  * readable length of the stream and never read outside it, whatever an (untrusted) offset table says; every decode call
  * uses its own device status word, so decodes on different streams of one context do not interfere.
- * One exception: the batched inflate (mi_inflate_batch_dev, mi_inflate_batch_size_dev) is asynchronous on `stream` under the
- * encoders' contract above — its verdicts are per item and stay on the device, so nothing needs a host round trip: scratch is
+ * One exception: the batched inflate (mi_inflate_batch_dev, mi_inflate_batch_size_dev) and the BGZF range read
+ * (mi_bgzf_read_ranges_dev) are asynchronous on `stream` under the encoders' contract above — their verdicts are per item and stay on the device, so nothing needs a host round trip: scratch is
  * the context workspace, the calls allocate or synchronise only while it grows, one call per context in flight at a time.
  */
 #ifndef MI_CODEC_H
@@ -471,6 +471,67 @@ mi_status mi_bgzf_inflate_dev(mi_ctx *ctx, const uint8_t *d_stream, uint64_t str
                               uint64_t first_member, uint64_t n_members, uint8_t *d_out, uint64_t out_bytes, uint32_t flags, void *stream);
 mi_status mi_bgzf_inflate(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint8_t *h_out, uint64_t out_cap,
                           uint64_t *h_out_bytes, uint32_t flags);
+
+/* ------------------------------------------------------------------------------------
+ * BGZF byte ranges: many (offset, length) slices of the UNCOMPRESSED data in one call — what
+ * tabix / BAI region queries and bgzf_seek + bgzf_read ask for, thousands at a time, each inside
+ * one to three members.  The pattern of the batch entry points below: device arrays in, one
+ * verdict per range on the device, one launch set; a bad range does not spoil the rest.
+ *
+ * d_members, n_members: the table mi_bgzf_index_dev wrote, n_members + 1 pairs.  Every other array
+ * is a DEVICE array of `count` entries.  Let total be the output offset of the last pair.  Range i
+ * is the bytes [d_off[i], min(d_off[i] + d_len[i], total)) of the inflated stream and is written at
+ * d_out + d_out_off[i]; its SLOT is [d_out_off[i], d_out_off[i] + d_len[i]).  out_bytes is the size
+ * of d_out: nothing is stored at or past it.  Ranges may overlap in the source, repeat and come in
+ * any order; their slots must not overlap — the library does NOT check that.  No alignment is
+ * required of d_out or the offsets; d_stream is 4-byte aligned, as for mi_bgzf_inflate_dev.
+ * Members with ISIZE 0 (empty members, the EOF member) contribute nothing and are skipped unread.
+ *
+ * Per range, on the device: d_status[i] (an mi_status) and d_got[i] —
+ *   MI_OK            d_got[i] = the bytes delivered: d_len[i], or fewer where the range ends past
+ *                    the end of the data (a short read, as bgzf_read gives); 0 for d_len[i] = 0 and
+ *                    for d_off[i] >= total.  The slot's bytes behind d_got[i] are left as they were.
+ *   MI_ERR_CORRUPT   d_got[i] = 0: a member the range touches fails the header re-check against
+ *                    the table, the decode (every condition of mi_bgzf_inflate_dev, per member) or,
+ *                    unless MI_INFLATE_NO_CHECKSUM is set, its CRC-32; a table that decreases where
+ *                    the range meets it, or holds no member for bytes below its total.  The slot's
+ *                    content is unspecified; nothing outside the slot is written.
+ *   MI_ERR_ARG       d_got[i] = 0: a slot (of d_len[i] > 0) that leaves [0, out_bytes) — nothing is
+ *                    written for it; pieces beyond max_pieces (below).
+ * *d_failed (may be NULL) = the number of ranges whose status is not MI_OK.
+ * max_pieces: a HOST-side upper bound on the number of PIECES, a piece being one (range, non-empty
+ * member) pair, so that grids and workspace are sized without reading the device — the max_blocks
+ * of mi_deflate_batch_dev.  mi_bgzf_read_max_pieces gives count + total_len / min_member_bytes +
+ * count from the sum of the lengths and the smallest non-empty member's uncompressed size (at most
+ * two cut members per range plus the whole ones that fit between them): MI_BGZF_BLOCK for the
+ * output of one bgzip run (only its last member is shorter, and the last member never lies
+ * between two others); for concatenated files, or foreign writers, the smallest member there is,
+ * or the exact count from the index.  Every piece of the bound costs a wave per stage whether a range fills it or
+ * not: keep it tight.  A range whose pieces do not fit the bound — the first such range and every
+ * range behind it — is MI_ERR_ARG; the ranges before it are unaffected.
+ * A piece whose member lies wholly inside the range is decoded straight into the slot; a member cut
+ * by the range's start or end is decoded whole into a 64 KiB cell of the context workspace (at most
+ * 4 096 cells, 256 MiB, used again group after group) and the slice copied out, so every member
+ * read is CRC-checked whole.
+ * The table is untrusted, exactly as for mi_bgzf_inflate_dev: the same bounds on stream reads, every
+ * loop bounded, writes inside the range's own slot.
+ * The call itself returns only MI_OK, MI_ERR_ARG (NULL arrays, d_stream not 4-byte aligned, unknown
+ * flag bits, count above 2^30 - 1, n_members or max_pieces above 2^31 - 1), MI_ERR_HIP or
+ * MI_ERR_NOMEM; count == 0 is MI_OK and launches nothing.  Asynchronous on `stream`: no host
+ * synchronisation and no device-to-host read once the workspace has grown; read the verdicts after
+ * mi_sync or in stream order.  It uses the context workspace: one call of a context in flight at a
+ * time.
+ * mi_bgzf_read_ranges: host buffers and host arrays — copy up (h_out too: what lies between the
+ * slots comes back as it was), index, read, copy down; it finds its own bound from the index.
+ * ------------------------------------------------------------------------------------ */
+uint64_t  mi_bgzf_read_max_pieces(uint64_t count, uint64_t total_len, uint64_t min_member_bytes);
+mi_status mi_bgzf_read_ranges_dev(mi_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes, const uint64_t *d_members,
+                                  uint64_t n_members, uint64_t count, const uint64_t *d_off, const uint64_t *d_len,
+                                  uint8_t *d_out, const uint64_t *d_out_off, uint64_t out_bytes, uint64_t max_pieces,
+                                  uint64_t *d_got, uint32_t *d_status, uint32_t *d_failed, uint32_t flags, void *stream);
+mi_status mi_bgzf_read_ranges(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint64_t count,
+                              const uint64_t *h_off, const uint64_t *h_len, uint8_t *h_out, const uint64_t *h_out_off,
+                              uint64_t out_bytes, uint64_t *h_got, uint32_t *h_status, uint32_t flags);
 
 /* ------------------------------------------------------------------------------------
  * Batched inflate: many independent DEFLATE streams in one launch — Parquet / ORC pages, zarr /
