@@ -119,47 +119,6 @@ extern "C" uint64_t mi_bgzf_bound_bytes(uint64_t n, const mi_lz_params *p)
     return (nblocks ? (nblocks - 1) * member(block) + member(last) : 0) + 28;
 }
 
-// host form: copy in, encode, copy out (the mi_encode_again_if_unstable rule of mi_deflate_h_encode)
-struct BgzfHostArgs { mi_ctx *ctx; const mi_lz_params *p; const uint8_t *h_in; uint64_t n; uint8_t *h_out; uint64_t cap;
-                      uint64_t *bits; uint64_t *out_bytes; };
-
-static mi_status bgzf_encode_host_once(const BgzfHostArgs &a)
-{
-    mi_status st = defz_check(a.p, MI_CONTAINER_RAW);
-    if (st) return st;
-    if (a.p->block > MI_BGZF_MAX_BLOCK) return MI_ERR_ARG;
-    const uint64_t bound = mi_bgzf_bound_bytes(a.n, a.p);
-    if (a.cap < bound) return MI_ERR_CAPACITY;
-    const uint64_t nblocks = (a.n + a.p->block - 1) / a.p->block;
-    hipStream_t s = mi_host_stream(a.ctx);
-    uint8_t *d_in = nullptr, *d_out = nullptr; uint64_t *d_bits = nullptr;
-    if (hipMalloc(&d_in, a.n + 64) != hipSuccess || hipMalloc(&d_out, bound + 64) != hipSuccess ||
-        hipMalloc(&d_bits, (nblocks + 2) * 8) != hipSuccess) st = MI_ERR_NOMEM;
-    if (st == MI_OK && a.n && hipMemcpyAsync(d_in, a.h_in, a.n, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) st = mi_bgzf_encode_dev(a.ctx, a.p, d_in, a.n, d_out, bound + 64, d_bits, d_bits + nblocks + 1, s);
-    uint64_t bytes = 0;
-    if (st == MI_OK && hipMemcpyAsync(a.bits, d_bits, (nblocks + 1) * 8, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipMemcpyAsync(&bytes, d_bits + nblocks + 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && bytes > a.cap) st = MI_ERR_CAPACITY;
-    if (st == MI_OK && hipMemcpy(a.h_out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && a.out_bytes) *a.out_bytes = bytes;
-    if (st == MI_ERR_HIP) a.ctx->last_hip = (int)hipGetLastError();
-    (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_bits);
-    return st;
-}
-
-extern "C" mi_status mi_bgzf_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n, uint8_t *h_out,
-                                    uint64_t cap_bytes, uint64_t *h_member_bits, uint64_t *h_out_bytes)
-{
-    if (!ctx || !p || !h_out || !h_member_bits || (n && !h_in)) return MI_ERR_ARG;
-    mi_order_poll(ctx);
-    const uint32_t seen = ctx->order_violations;
-    BgzfHostArgs a{ctx, p, h_in, n, h_out, cap_bytes, h_member_bits, h_out_bytes};
-    return mi_encode_again_if_unstable(ctx, seen, bgzf_encode_host_once(a),
-        [](void *v) { return bgzf_encode_host_once(*(BgzfHostArgs *)v); }, &a);
-}
-
 // ---------------------------------------------------------------------------------------------
 // read: the member header
 // ---------------------------------------------------------------------------------------------
@@ -412,29 +371,4 @@ extern "C" mi_status mi_bgzf_inflate_dev(mi_ctx *ctx, const uint8_t *d_stream, u
     MI_HIP(ctx, hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, s));
     MI_HIP(ctx, hipStreamSynchronize(s));
     return h_err ? MI_ERR_CORRUPT : MI_OK;
-}
-
-// host buffers: copy in, count, index, inflate everything, copy out
-extern "C" mi_status mi_bgzf_inflate(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint8_t *h_out, uint64_t out_cap,
-                                     uint64_t *h_out_bytes, uint32_t flags)
-{
-    if (!ctx || (stream_bytes && !h_stream) || (out_cap && !h_out)) return MI_ERR_ARG;
-    if (flags & ~MI_INFLATE_NO_CHECKSUM) return MI_ERR_ARG;
-    hipStream_t s = mi_host_stream(ctx);
-    uint8_t *d_stream = nullptr, *d_out = nullptr; uint64_t *d_count = nullptr, *d_members = nullptr;
-    mi_status st = MI_OK;
-    uint64_t cnt[2] = {0, 0};
-    if (hipMalloc(&d_stream, stream_bytes + 64) != hipSuccess || hipMalloc(&d_count, 16) != hipSuccess) st = MI_ERR_NOMEM;
-    if (st == MI_OK && stream_bytes && hipMemcpyAsync(d_stream, h_stream, stream_bytes, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) st = mi_bgzf_index_dev(ctx, d_stream, stream_bytes, nullptr, 0, d_count, s);
-    if (st == MI_OK && hipMemcpy(cnt, d_count, 16, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && cnt[1] > out_cap) st = MI_ERR_CAPACITY;
-    if (st == MI_OK && (hipMalloc(&d_members, (cnt[0] + 1) * 16) != hipSuccess || hipMalloc(&d_out, cnt[1] + 16) != hipSuccess)) st = MI_ERR_NOMEM;
-    if (st == MI_OK) st = mi_bgzf_index_dev(ctx, d_stream, stream_bytes, d_members, cnt[0], d_count, s);
-    if (st == MI_OK) st = mi_bgzf_inflate_dev(ctx, d_stream, stream_bytes, d_members, 0, cnt[0], d_out, cnt[1], flags, s);
-    if (st == MI_OK && cnt[1] && hipMemcpy(h_out, d_out, cnt[1], hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && h_out_bytes) *h_out_bytes = cnt[1];
-    if (st == MI_ERR_HIP && !ctx->last_hip) ctx->last_hip = (int)hipGetLastError();
-    (void)hipFree(d_stream); (void)hipFree(d_count); (void)hipFree(d_members); (void)hipFree(d_out);
-    return st;
 }

@@ -28,10 +28,7 @@
 #include "lz_common.h"
 #include "internal.h"
 #include "bgzf_core.h"
-#include <stdlib.h>
-#include <string.h>
 
-#define BGZR_MAX     0x7FFFFFFFull             // ranges, members and pieces per call: their numbers are 32-bit
 #define BGZR_CELL    65536u                    // a member inflates to at most this
 #define BGZR_GROUP   4096u                     // edge slots decoded per launch set: 256 MiB of scratch at most
 #define BGZR_HEAD    256u                      // workspace head: u32 nnz (non-empty members), u32 nreal (pieces)
@@ -326,65 +323,4 @@ extern "C" mi_status mi_bgzf_read_ranges_dev(mi_ctx *ctx, const uint8_t *d_strea
     }
     MI_HIP(ctx, hipGetLastError());
     return MI_OK;
-}
-
-// host buffers: copy up, index (count, then the table), read, copy down.  The bound on the pieces comes from the table
-// itself: the members, empty ones included, between the first one that holds a byte of the range and the last.
-extern "C" mi_status mi_bgzf_read_ranges(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint64_t count,
-                                         const uint64_t *h_off, const uint64_t *h_len, uint8_t *h_out, const uint64_t *h_out_off,
-                                         uint64_t out_bytes, uint64_t *h_got, uint32_t *h_status, uint32_t flags)
-{
-    if (!ctx || (stream_bytes && !h_stream) || (out_bytes && !h_out)) return MI_ERR_ARG;
-    if ((flags & ~MI_INFLATE_NO_CHECKSUM) || count > BGZR_MAX / 2u) return MI_ERR_ARG;
-    if (count == 0) return MI_OK;
-    if (!h_off || !h_len || !h_out_off || !h_got || !h_status) return MI_ERR_ARG;
-    hipStream_t s = mi_host_stream(ctx);
-    uint8_t *d_stream = nullptr, *d_out = nullptr; uint64_t *d_count = nullptr, *d_members = nullptr, *d_arr = nullptr;
-    uint64_t *h_members = nullptr;
-    mi_status st = MI_OK;
-    uint64_t cnt[2] = {0, 0};
-    const size_t arr = mi_align_up((size_t)count * 8u, 256);           // [off | len | out off | got | status]
-    if (hipMalloc(&d_stream, stream_bytes + 64) != hipSuccess || hipMalloc(&d_count, 16) != hipSuccess ||
-        hipMalloc(&d_arr, 5 * arr) != hipSuccess || hipMalloc(&d_out, out_bytes + 16) != hipSuccess) st = MI_ERR_NOMEM;
-    if (st == MI_OK && stream_bytes && hipMemcpyAsync(d_stream, h_stream, stream_bytes, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) st = mi_bgzf_index_dev(ctx, d_stream, stream_bytes, nullptr, 0, d_count, s);
-    if (st == MI_OK && hipMemcpy(cnt, d_count, 16, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && cnt[0] > BGZR_MAX) st = MI_ERR_ARG;
-    if (st == MI_OK && (hipMalloc(&d_members, (cnt[0] + 1) * 16) != hipSuccess || !(h_members = (uint64_t *)malloc((cnt[0] + 1) * 16)))) st = MI_ERR_NOMEM;
-    if (st == MI_OK) st = mi_bgzf_index_dev(ctx, d_stream, stream_bytes, d_members, cnt[0], d_count, s);
-    if (st == MI_OK && hipMemcpy(h_members, d_members, (cnt[0] + 1) * 16, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    uint64_t max_pieces = 0;
-    if (st == MI_OK) {
-        // (the index's own table: its output offsets do not decrease)
-        const uint64_t nm = cnt[0], total = cnt[1];
-        auto o = [&](uint64_t m) { return h_members[2 * m + 1]; };
-        for (uint64_t i = 0; i < count; ++i) {
-            const uint64_t a = h_off[i], len = h_len[i];
-            if (!len || a >= total) continue;
-            const uint64_t b = len < total - a ? a + len : total;
-            uint64_t lo = 0, hi = nm;                                   // the first member that ends behind a
-            while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (o(mid + 1) > a) hi = mid; else lo = mid + 1; }
-            const uint64_t m0 = lo;
-            hi = nm;                                                    // the first member at or behind m0 that starts at or behind b
-            while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (o(mid) >= b) hi = mid; else lo = mid + 1; }
-            max_pieces += lo - m0;
-        }
-        if (max_pieces > BGZR_MAX) st = MI_ERR_ARG;
-    }
-    if (st == MI_OK && (hipMemcpyAsync(d_arr, h_off, count * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-                        hipMemcpyAsync((uint8_t *)d_arr + arr, h_len, count * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-                        hipMemcpyAsync((uint8_t *)d_arr + 2 * arr, h_out_off, count * 8, hipMemcpyHostToDevice, s) != hipSuccess)) st = MI_ERR_HIP;
-    if (st == MI_OK && out_bytes && hipMemcpyAsync(d_out, h_out, out_bytes, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;   // what lies between the slots stays
-    if (st == MI_OK)
-        st = mi_bgzf_read_ranges_dev(ctx, d_stream, stream_bytes, d_members, cnt[0], count, d_arr, (const uint64_t *)((uint8_t *)d_arr + arr),
-                                     d_out, (const uint64_t *)((uint8_t *)d_arr + 2 * arr), out_bytes, max_pieces,
-                                     (uint64_t *)((uint8_t *)d_arr + 3 * arr), (uint32_t *)((uint8_t *)d_arr + 4 * arr), nullptr, flags, s);
-    if (st == MI_OK && hipMemcpyAsync(h_got, (uint8_t *)d_arr + 3 * arr, count * 8, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipMemcpyAsync(h_status, (uint8_t *)d_arr + 4 * arr, count * 4, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && out_bytes && hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_ERR_HIP && !ctx->last_hip) ctx->last_hip = (int)hipGetLastError();
-    (void)hipFree(d_stream); (void)hipFree(d_count); (void)hipFree(d_arr); (void)hipFree(d_out); (void)hipFree(d_members);
-    free(h_members);
-    return st;
 }

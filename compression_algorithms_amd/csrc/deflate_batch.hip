@@ -25,10 +25,7 @@
 #include "crc32.h"
 #include "adler32.h"
 #include "internal.h"
-#include <stdlib.h>
-#include <string.h>
 
-#define DFB_MAX_BYTES 0x7FFFFFFFull            // per item and per count: block numbers and positions inside an item are 32-bit
 #define DFB_HEAD      256u                     // workspace head: u32 nreal, u64 carry[2] at byte 8, a zero byte at byte 64 (the PAD block)
 
 struct DfbWs {
@@ -306,90 +303,4 @@ extern "C" mi_status mi_deflate_batch_dev(mi_ctx *ctx, const mi_lz_params *p, ui
     const DfbCall b{container, count, max_blocks, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, d_failed};
     const DefzCall z{container, nullptr, false, &b};
     return lz_encode_impl(ctx, p, nullptr, 0, nullptr, 0, nullptr, stream, 2, &z);
-}
-
-// host buffers: the items packed into one device buffer (each at a 16-byte boundary), the outputs likewise by their capacities;
-// copy up, encode, copy down what came out MI_OK (the one-more-try rule of the host-buffer encoders, host_api.hip)
-struct DfbHostArgs { mi_ctx *ctx; const mi_lz_params *p; uint32_t container; uint64_t count; const void *const *h_in; const uint64_t *h_in_bytes;
-                     void *const *h_out; const uint64_t *h_out_cap; uint64_t *h_out_bytes; uint32_t *h_status; };
-
-static mi_status dfb_host_once(const DfbHostArgs &a)
-{
-    mi_ctx *ctx = a.ctx;
-    const uint64_t count = a.count;
-    // an item the device answers with MI_ERR_ARG takes no room here: its (bad) pointer and size go up as they are
-    auto in_ok = [&](uint64_t i) { return a.h_in_bytes[i] <= DFB_MAX_BYTES && (a.h_in[i] || !a.h_in_bytes[i]); };
-    auto out_ok = [&](uint64_t i) { return a.h_out_cap[i] <= DFB_MAX_BYTES && (a.h_out[i] || !a.h_out_cap[i]); };
-    uint64_t in_total = 0, out_total = 0, max_blocks = 0;
-    for (uint64_t i = 0; i < count; ++i) {
-        if (in_ok(i)) { in_total += mi_align_up(a.h_in_bytes[i], 16); max_blocks += (a.h_in_bytes[i] + a.p->block - 1) / a.p->block; }
-        if (out_ok(i)) out_total += mi_align_up(a.h_out_cap[i], 16);
-    }
-    if (max_blocks > DFB_MAX_BYTES) return MI_ERR_ARG;
-    hipStream_t s = mi_host_stream(ctx);
-    mi_status st = MI_OK;
-    const size_t arr = mi_align_up((size_t)count * 8u, 256);
-    // host staging: [in ptrs | in bytes | out ptrs | out caps | out bytes | status], the packed inputs, the packed outputs
-    uint8_t *h_arr = (uint8_t *)calloc(6, arr), *h_pack = (uint8_t *)malloc(in_total + 16), *h_res = (uint8_t *)malloc(out_total + 16);
-    uint8_t *d_arr = nullptr, *d_pack = nullptr, *d_res = nullptr;
-    if (!h_arr || !h_pack || !h_res) st = MI_ERR_NOMEM;
-    if (st == MI_OK && (hipMalloc(&d_arr, 6 * arr) != hipSuccess || hipMalloc(&d_pack, in_total + 64) != hipSuccess ||
-                        hipMalloc(&d_res, out_total + 64) != hipSuccess)) st = MI_ERR_NOMEM;
-    if (st == MI_OK) {
-        uint64_t *p_in = (uint64_t *)h_arr, *p_nb = (uint64_t *)(h_arr + arr), *p_out = (uint64_t *)(h_arr + 2 * arr),
-                 *p_cap = (uint64_t *)(h_arr + 3 * arr);
-        uint64_t at = 0, ot = 0;
-        for (uint64_t i = 0; i < count; ++i) {
-            p_nb[i] = a.h_in_bytes[i];
-            if (in_ok(i)) {
-                p_in[i] = (uint64_t)(uintptr_t)(d_pack + at);
-                if (a.h_in_bytes[i]) memcpy(h_pack + at, a.h_in[i], a.h_in_bytes[i]);
-                at += mi_align_up(a.h_in_bytes[i], 16);
-            } else p_in[i] = a.h_in[i] ? (uint64_t)(uintptr_t)d_pack : 0u;
-            p_cap[i] = a.h_out_cap[i];
-            if (out_ok(i)) { p_out[i] = (uint64_t)(uintptr_t)(d_res + ot); ot += mi_align_up(a.h_out_cap[i], 16); }
-            else p_out[i] = a.h_out[i] ? (uint64_t)(uintptr_t)d_res : 0u;
-        }
-        if (hipMemcpyAsync(d_arr, h_arr, 4 * arr, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-        if (st == MI_OK && in_total && hipMemcpyAsync(d_pack, h_pack, in_total, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    }
-    if (st == MI_OK)
-        st = mi_deflate_batch_dev(ctx, a.p, a.container, count, (const void *const *)d_arr, (const uint64_t *)(d_arr + arr), max_blocks,
-                                  (void *const *)(d_arr + 2 * arr), (const uint64_t *)(d_arr + 3 * arr), (uint64_t *)(d_arr + 4 * arr),
-                                  (uint32_t *)(d_arr + 5 * arr), nullptr, s);
-    if (st == MI_OK && hipMemcpyAsync(h_arr + 4 * arr, d_arr + 4 * arr, 2 * arr, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && out_total && hipMemcpyAsync(h_res, d_res, out_total, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) {
-        const uint64_t *r_nb = (const uint64_t *)(h_arr + 4 * arr);
-        const uint32_t *r_st = (const uint32_t *)(h_arr + 5 * arr);
-        uint64_t ot = 0;
-        for (uint64_t i = 0; i < count; ++i) {
-            a.h_out_bytes[i] = r_nb[i];
-            a.h_status[i] = r_st[i];
-            if (!out_ok(i)) continue;
-            if (r_st[i] == MI_OK && r_nb[i]) memcpy(a.h_out[i], h_res + ot, r_nb[i]);
-            ot += mi_align_up(a.h_out_cap[i], 16);
-        }
-    }
-    if (st == MI_ERR_HIP && !ctx->last_hip) ctx->last_hip = (int)hipGetLastError();
-    (void)hipFree(d_arr); (void)hipFree(d_pack); (void)hipFree(d_res);
-    free(h_arr); free(h_pack); free(h_res);
-    return st;
-}
-
-extern "C" mi_status mi_deflate_batch(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
-                                      const void *const *h_in, const uint64_t *h_in_bytes,
-                                      void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status)
-{
-    if (!ctx) return MI_ERR_ARG;
-    mi_status st = defz_check(p, container);
-    if (st) return st;
-    if (count > DFB_MAX_BYTES) return MI_ERR_ARG;
-    if (count == 0) return MI_OK;
-    if (!h_in || !h_in_bytes || !h_out || !h_out_cap || !h_out_bytes || !h_status) return MI_ERR_ARG;
-    mi_order_poll(ctx);
-    const uint32_t seen = ctx->order_violations;
-    DfbHostArgs a{ctx, p, container, count, h_in, h_in_bytes, h_out, h_out_cap, h_out_bytes, h_status};
-    return mi_encode_again_if_unstable(ctx, seen, dfb_host_once(a), [](void *v) { return dfb_host_once(*(DfbHostArgs *)v); }, &a);
 }

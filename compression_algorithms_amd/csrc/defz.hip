@@ -616,43 +616,3 @@ extern "C" mi_status mi_adler32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n
     if (st) return st;
     return zck_launch(ctx, false, d_in, n, (uint32_t *)ctx->ws, d_adler, (hipStream_t)stream);
 }
-
-// host form: copy in, encode, copy out (the mi_encode_again_if_unstable rule of mi_deflate_h_encode)
-struct DefzHostArgs { mi_ctx *ctx; const mi_lz_params *p; uint32_t container; const uint8_t *h_in; uint64_t n; uint8_t *h_out; uint64_t cap;
-                      uint64_t *bits; uint64_t *out_bytes; };
-
-static mi_status defz_encode_host_once(const DefzHostArgs &a)
-{
-    mi_status st = defz_check(a.p, a.container);
-    if (st) return st;
-    const uint64_t bound = mi_deflate_z_bound_bytes(a.n, a.p, a.container);
-    if (a.cap < bound) return MI_ERR_CAPACITY;
-    const uint64_t nblocks = (a.n + a.p->block - 1) / a.p->block;
-    hipStream_t s = mi_host_stream(a.ctx);
-    uint8_t *d_in = nullptr, *d_out = nullptr; uint64_t *d_bits = nullptr;
-    if (hipMalloc(&d_in, a.n + 64) != hipSuccess || hipMalloc(&d_out, bound + 64) != hipSuccess ||
-        hipMalloc(&d_bits, (nblocks + 2) * 8) != hipSuccess) st = MI_ERR_NOMEM;
-    if (st == MI_OK && a.n && hipMemcpyAsync(d_in, a.h_in, a.n, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) st = mi_deflate_z_encode_dev(a.ctx, a.p, a.container, d_in, a.n, d_out, bound + 64, d_bits, d_bits + nblocks + 1, s);
-    uint64_t bytes = 0;
-    if (st == MI_OK && hipMemcpyAsync(a.bits, d_bits, (nblocks + 1) * 8, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipMemcpyAsync(&bytes, d_bits + nblocks + 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && bytes > a.cap) st = MI_ERR_CAPACITY;
-    if (st == MI_OK && hipMemcpy(a.h_out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && a.out_bytes) *a.out_bytes = bytes;
-    if (st == MI_ERR_HIP) a.ctx->last_hip = (int)hipGetLastError();
-    (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_bits);
-    return st;
-}
-
-extern "C" mi_status mi_deflate_z_encode(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, const uint8_t *h_in, uint64_t n,
-                                         uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, uint64_t *h_out_bytes)
-{
-    if (!ctx || !p || !h_out || !h_block_bits || (n && !h_in)) return MI_ERR_ARG;
-    mi_order_poll(ctx);
-    const uint32_t seen = ctx->order_violations;
-    DefzHostArgs a{ctx, p, container, h_in, n, h_out, cap_bytes, h_block_bits, h_out_bytes};
-    return mi_encode_again_if_unstable(ctx, seen, defz_encode_host_once(a),
-        [](void *v) { return defz_encode_host_once(*(DefzHostArgs *)v); }, &a);
-}

@@ -1,19 +1,54 @@
-// host_api.hip — host-buffer convenience entry points: copy in, run the *_dev path on the
-// context's private stream, copy out, synchronise.  The PCIe-inclusive path of the drop-in
-// libraries (dropin_*.c); throughput numbers are quoted on the *_dev entry points.
+// host_api.hip — every host-buffer convenience entry point of the library: copy in, run the public *_dev path on the
+// context's private stream, copy out, synchronise.  The PCIe-inclusive path of the drop-in libraries (dropin_*.c);
+// throughput numbers are quoted on the *_dev entry points.  No kernel lives here and nothing here is on the hot path.
+//
+//   the owners of the buffers, the one-more-try rule of the encoders
+//   the chunked (pipelined) paths of the byte-aligned block formats, both directions
+//   Huffman, the block formats (tokens, mode H, mode Z, BGZF, FSE), inflate, the whole-buffer lz77 forms
+//   the batches (inflate, deflate) and their one staging routine; BGZF read from host bytes (inflate, ranges)
+//
+// One error convention: a HIP call that fails stores its own code in ctx->last_hip and the entry point returns MI_ERR_HIP
+// (MI_HIP, common.h); an allocation that fails is MI_ERR_NOMEM.
 #include "common.h"
 #include "internal.h"
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
+// The owners of an entry point's buffers.  Nothing may outlive the buffers: a DevBuf's hipFree waits for the device, so no
+// kernel or copy still touches device memory when it goes; host staging (HostBuf) is DECLARED BEFORE the DevBufs of its
+// function, hence destroyed after them — after that wait — so no copy on the stream still reads or writes it.
 struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
     bool alloc(size_t n) { return hipMalloc(&p, n ? n : 16) == hipSuccess; }
     template <typename T> T *as() { return reinterpret_cast<T *>(p); }
 };
+struct HostBuf {
+    void *p = nullptr;
+    ~HostBuf() { free(p); }
+    bool alloc(size_t n) { return (p = malloc(n)) != nullptr; }
+    bool zalloc(size_t n) { return (p = calloc(1, n)) != nullptr; }
+    template <typename T> T *as() { return reinterpret_cast<T *>(p); }
+};
 }
 
+// A synchronous entry point has its result in hand when it returns, so an order violation reported while it ran (lz_common.h
+// lz_order_violation) is repaired here: the context has switched to ballot ranking, the call encodes once more.
+template <class Once> static mi_status host_encode_with_retry(mi_ctx *ctx, Once once)
+{
+    mi_order_poll(ctx);
+    const uint32_t seen_before = ctx->order_violations;
+    mi_status st = once();
+    mi_order_poll(ctx);                                                     // (chunked paths poll between their chunks too)
+    if (st != MI_OK || ctx->order_violations == seen_before) return st;
+    const uint32_t seen = ctx->order_violations;
+    st = once();
+    mi_order_poll(ctx);
+    if (st == MI_OK && ctx->order_violations != seen) st = MI_ERR_UNSTABLE; // ballots cannot mis-rank: this does not happen
+    ctx->order_reported = ctx->order_violations;                            // handled here: mi_sync need not repeat it
+    return st;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Host buffers larger than one chunk, byte-aligned formats (deflate tokens, mode H): the input goes up and the stream comes
@@ -33,13 +68,13 @@ static uint64_t host_chunk_blocks()
     return (uint64_t)v;
 }
 
-mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_in, uint64_t n,
-                                   uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, bool *done)
+static mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_in, uint64_t n,
+                                          uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, bool *done)
 {
     *done = false;
     const uint64_t cb = host_chunk_blocks(), C = cb * (uint64_t)p->block;
     if (!p->deflate || n <= C || !ctx->h_pinned || ctx->h_pinned_bytes < 2 * (cb + 1) * 8) return MI_OK;      // the caller's one-shot path
-    const uint64_t nchunks = (n + C - 1) / C, nblocks = (n + p->block - 1) / p->block;
+    const uint64_t nchunks = (n + C - 1) / C;
     const uint64_t cbound = (mode_h ? mi_deflate_h_bound_bytes(C, p) : mi_lz_bound_bytes(C, p)) + 64;
     hipStream_t s = mi_host_stream(ctx), cin = nullptr, cout = nullptr;
     hipEvent_t ev_in[2] = {}, ev_enc[2] = {}, ev_out[2] = {};
@@ -91,8 +126,7 @@ mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_
         if (hipEventRecord(ev_out[b], cout) != hipSuccess) { st = MI_ERR_HIP; break; }
         base_bits += cbits[nb];
     }
-    (void)nblocks;
-    // nothing may outlive the buffers: drain all three streams whatever happened
+    // the owners' rule (above), and the copy streams and events are destroyed next: drain all three streams whatever happened
     if (cin) (void)hipStreamSynchronize(cin);
     (void)hipStreamSynchronize(s);
     if (cout) (void)hipStreamSynchronize(cout);
@@ -182,7 +216,7 @@ static mi_status mi_decode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, in
         if (hipStreamWaitEvent(cout, ev_dec[c % NE], 0) != hipSuccess ||
             hipMemcpyAsync(h_out + c * C, out.as<uint8_t>() + c * C, chunk_len(c), hipMemcpyDeviceToHost, cout) != hipSuccess) { st = MI_ERR_HIP; break; }
     }
-    // nothing may outlive the buffers: drain every stream whatever happened
+    // the owners' rule (above), and the streams and events are destroyed next: drain every stream whatever happened
     if (cin) (void)hipStreamSynchronize(cin);
     for (uint32_t k = 0; k < 4; ++k) if (k == 0 || sx[k]) (void)hipStreamSynchronize(sx[k]);
     if (cout) (void)hipStreamSynchronize(cout);
@@ -196,6 +230,31 @@ static mi_status mi_decode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, in
     if (st == MI_OK && h_err) st = MI_ERR_CORRUPT;       // (the caller's buffer may hold the chunks that came down before the bad one)
     if (st == MI_OK) *done = true;
     return st;
+}
+
+extern "C" mi_status mi_huffman_encode(mi_ctx *ctx, const uint8_t *h_in, uint64_t n, uint32_t *h_words,
+                                       uint64_t cap_words, mi_huffman_info *h_info, mi_huffman_tree *h_tree)
+{
+    if (!ctx || !h_words || !h_info || (n && !h_in)) return MI_ERR_ARG;
+    hipStream_t s = mi_host_stream(ctx);
+    // reserve the kernels' workspace first: growing it later would synchronise mid-sequence
+    mi_status st = mi_ws_reserve(ctx, huff_ws_bytes(n));
+    if (st) return st;
+    DevBuf in, words, info, tree;
+    if (!in.alloc(n + 16) || !words.alloc(cap_words * 4) || !info.alloc(sizeof(mi_huffman_info)) ||
+        !tree.alloc(sizeof(mi_huffman_tree))) return MI_ERR_NOMEM;
+    if (n) MI_HIP(ctx, hipMemcpyAsync(in.p, h_in, n, hipMemcpyHostToDevice, s));
+    st = mi_huffman_encode_dev(ctx, in.as<uint8_t>(), n, words.as<uint32_t>(), cap_words, info.as<mi_huffman_info>(),
+                               tree.as<mi_huffman_tree>(), nullptr, s);
+    if (st) return st;
+    MI_HIP(ctx, hipMemcpyAsync(h_info, info.p, sizeof(*h_info), hipMemcpyDeviceToHost, s));
+    MI_HIP(ctx, hipStreamSynchronize(s));
+    if (h_tree) MI_HIP(ctx, hipMemcpy(h_tree, tree.p, sizeof(*h_tree), hipMemcpyDeviceToHost));
+    if (h_info->status != MI_OK) return (mi_status)h_info->status;
+    const uint64_t nw = (h_info->total_bits + 31) >> 5;
+    if (nw > cap_words) return MI_ERR_CAPACITY;
+    if (nw) MI_HIP(ctx, hipMemcpy(h_words, words.p, nw * 4, hipMemcpyDeviceToHost));
+    return MI_OK;
 }
 
 extern "C" mi_status mi_huffman_encode2(mi_ctx *ctx, const uint8_t *h_in, uint64_t n, uint32_t *h_words, uint64_t cap_words,
@@ -299,97 +358,115 @@ extern "C" mi_status mi_huffman_encode_with_codes(mi_ctx *ctx, const uint8_t *h_
     return MI_OK;
 }
 
-extern "C" mi_status mi_lz_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_stream, uint64_t stream_bytes,
-                                  const uint64_t *h_block_bits, uint8_t *h_out, uint64_t n)
+// ---------------------------------------------------------------------------------------------------------------------
+// The block formats, one shot: everything up, the *_dev call, everything down.
+// ---------------------------------------------------------------------------------------------------------------------
+// How an encoder's stream length is learned once its table is down: the table's last entry rounded up to bytes (tokens: the
+// lz77 flavour ends inside a byte), the same in whole bytes (mode H), or the out_bytes word the encoder writes behind the
+// table (mode Z, BGZF: containers and the EOF member are not in the table).
+enum BytesFrom { TABLE_BITS_ROUNDED_UP, TABLE_BITS_WHOLE, OUT_BYTES_WORD };
+
+// enc(d_in, d_out, cap, d_block_bits, d_out_bytes, s): the *_dev call; d_out_bytes is there with OUT_BYTES_WORD only
+template <class Enc>
+static mi_status block_encode_once(mi_ctx *ctx, const uint8_t *h_in, uint64_t n, uint64_t nblocks, uint64_t bound, BytesFrom from,
+                                   uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, uint64_t *h_out_bytes, Enc enc)
 {
-    if (!ctx || !p || !h_stream || !h_block_bits || (n && !h_out) || !p->block) return MI_ERR_ARG;
-    if (n == 0) return MI_OK;
     hipStream_t s = mi_host_stream(ctx);
-    const uint64_t nblocks = (n + p->block - 1) / p->block;
-    // the table indexes the stream: check it before anything is copied or launched
-    mi_status st = mi_validate_block_table(h_block_bits, nblocks, stream_bytes, p->deflate ? 8u : 1u);
+    const bool word = from == OUT_BYTES_WORD;
+    DevBuf in, out, bits;
+    if (!in.alloc(n + 64) || !out.alloc(bound + 64) || !bits.alloc((nblocks + 1 + word) * 8)) return MI_ERR_NOMEM;
+    if (n) MI_HIP(ctx, hipMemcpyAsync(in.p, h_in, n, hipMemcpyHostToDevice, s));
+    mi_status st = enc(in.as<uint8_t>(), out.as<uint8_t>(), bound + 64, bits.as<uint64_t>(), bits.as<uint64_t>() + nblocks + 1, s);
     if (st) return st;
-    {
-        bool done = false;
-        st = mi_decode_host_pipelined(ctx, p, 0, h_stream, stream_bytes, h_block_bits, h_out, n, &done);
-        if (st || done) return st;
-    }
-    DevBuf st_, bits, out;
-    if (!st_.alloc(stream_bytes + 64) || !bits.alloc((nblocks + 1) * 8) || !out.alloc(n + 16)) return MI_ERR_NOMEM;
-    MI_HIP(ctx, hipMemsetAsync(st_.as<uint8_t>() + stream_bytes, 0, 64, s));
-    MI_HIP(ctx, hipMemcpyAsync(st_.p, h_stream, stream_bytes, hipMemcpyHostToDevice, s));
-    MI_HIP(ctx, hipMemcpyAsync(bits.p, h_block_bits, (nblocks + 1) * 8, hipMemcpyHostToDevice, s));
-    st = mi_lz_decode_dev(ctx, p, st_.as<uint8_t>(), stream_bytes, bits.as<uint64_t>(), out.as<uint8_t>(), n, s);
-    if (st) return st;
-    MI_HIP(ctx, hipMemcpy(h_out, out.p, n, hipMemcpyDeviceToHost));
+    uint64_t bytes = 0;
+    MI_HIP(ctx, hipMemcpyAsync(h_block_bits, bits.p, (nblocks + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (word) MI_HIP(ctx, hipMemcpyAsync(&bytes, bits.as<uint64_t>() + nblocks + 1, 8, hipMemcpyDeviceToHost, s));
+    MI_HIP(ctx, hipStreamSynchronize(s));
+    if (!word) bytes = (h_block_bits[nblocks] + (from == TABLE_BITS_ROUNDED_UP ? 7 : 0)) / 8;
+    if (bytes > cap_bytes) return MI_ERR_CAPACITY;       // (tokens, Z, BGZF: the caller's capacity is at least the bound already)
+    if (bytes) MI_HIP(ctx, hipMemcpy(h_out, out.p, bytes, hipMemcpyDeviceToHost));
+    if (h_out_bytes) *h_out_bytes = bytes;
     return MI_OK;
 }
 
-static mi_status deflate_h_encode_once(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
-                                       uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits);
-
-// A synchronous entry point has its result in hand when it returns, so an order violation reported while it ran (lz_common.h
-// lz_order_violation) is repaired here: the context has switched to ballot ranking, the call encodes once more.
-mi_status mi_encode_again_if_unstable(mi_ctx *ctx, uint32_t seen_before, mi_status st, mi_status (*again)(void *), void *arg)
+extern "C" mi_status mi_lz_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
+                                  uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits)
 {
-    mi_order_poll(ctx);                                                     // (chunked paths poll between their chunks too)
-    if (st != MI_OK || ctx->order_violations == seen_before) return st;
-    const uint32_t seen = ctx->order_violations;
-    st = again(arg);
-    mi_order_poll(ctx);
-    if (st == MI_OK && ctx->order_violations != seen) st = MI_ERR_UNSTABLE; // ballots cannot mis-rank: this does not happen
-    ctx->order_reported = ctx->order_violations;                            // handled here: mi_sync need not repeat it
-    return st;
+    if (!ctx || !h_out || !h_block_bits || (n && !h_in) || !p) return MI_ERR_ARG;
+    return host_encode_with_retry(ctx, [&]() -> mi_status {
+        const uint64_t nblocks = p->block ? (n + p->block - 1) / p->block : 0;
+        const uint64_t bound = mi_lz_bound_bytes(n, p);
+        if (cap_bytes < bound) return MI_ERR_CAPACITY;
+        if (lz_check_params(p) == MI_OK && p->deflate) {       // byte tokens: chunks overlap their transfers with the encoder
+            bool done = false;
+            const mi_status ps = mi_encode_host_pipelined(ctx, p, 0, h_in, n, h_out, cap_bytes, h_block_bits, &done);
+            if (ps || done) return ps;
+        }
+        return block_encode_once(ctx, h_in, n, nblocks, bound, TABLE_BITS_ROUNDED_UP, h_out, cap_bytes, h_block_bits, nullptr,
+            [&](uint8_t *d_in, uint8_t *d_out, uint64_t cap, uint64_t *d_bits, uint64_t *, hipStream_t s) {
+                return mi_lz_encode_dev(ctx, p, d_in, n, d_out, cap, d_bits, s); });
+    });
 }
-
-struct HostEncArgs { mi_ctx *ctx; const mi_lz_params *p; const uint8_t *h_in; uint64_t n; uint8_t *h_out; uint64_t cap; uint64_t *bits; };
 
 extern "C" mi_status mi_deflate_h_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
                                          uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits)
 {
     if (!ctx || !p || !h_out || !h_block_bits || (n && !h_in) || !p->block) return MI_ERR_ARG;
-    mi_order_poll(ctx);
-    const uint32_t seen = ctx->order_violations;
-    HostEncArgs a{ctx, p, h_in, n, h_out, cap_bytes, h_block_bits};
-    return mi_encode_again_if_unstable(ctx, seen, deflate_h_encode_once(ctx, p, h_in, n, h_out, cap_bytes, h_block_bits),
-        [](void *v) { HostEncArgs *q = (HostEncArgs *)v; return deflate_h_encode_once(q->ctx, q->p, q->h_in, q->n, q->h_out, q->cap, q->bits); }, &a);
-}
-
-static mi_status deflate_h_encode_once(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
-                                       uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits)
-{
-    {
+    return host_encode_with_retry(ctx, [&]() -> mi_status {
         bool done = false;
         const mi_status ps = mi_encode_host_pipelined(ctx, p, 1, h_in, n, h_out, cap_bytes, h_block_bits, &done);
         if (ps || done) return ps;
-    }
-    hipStream_t s = mi_host_stream(ctx);
-    const uint64_t nblocks = (n + p->block - 1) / p->block, bound = mi_deflate_h_bound_bytes(n, p);
-    DevBuf in, out, bits;
-    if (!in.alloc(n + 64) || !out.alloc(bound + 64) || !bits.alloc((nblocks + 1) * 8)) return MI_ERR_NOMEM;
-    if (n) MI_HIP(ctx, hipMemcpyAsync(in.p, h_in, n, hipMemcpyHostToDevice, s));
-    mi_status st = mi_deflate_h_encode_dev(ctx, p, in.as<uint8_t>(), n, out.as<uint8_t>(), bound + 64, bits.as<uint64_t>(), s);
-    if (st) return st;
-    MI_HIP(ctx, hipMemcpyAsync(h_block_bits, bits.p, (nblocks + 1) * 8, hipMemcpyDeviceToHost, s));
-    MI_HIP(ctx, hipStreamSynchronize(s));
-    const uint64_t bytes = h_block_bits[nblocks] / 8;
-    if (bytes > cap_bytes) return MI_ERR_CAPACITY;
-    if (bytes) MI_HIP(ctx, hipMemcpy(h_out, out.p, bytes, hipMemcpyDeviceToHost));
-    return MI_OK;
+        const uint64_t nblocks = (n + p->block - 1) / p->block, bound = mi_deflate_h_bound_bytes(n, p);
+        return block_encode_once(ctx, h_in, n, nblocks, bound, TABLE_BITS_WHOLE, h_out, cap_bytes, h_block_bits, nullptr,
+            [&](uint8_t *d_in, uint8_t *d_out, uint64_t cap, uint64_t *d_bits, uint64_t *, hipStream_t s) {
+                return mi_deflate_h_encode_dev(ctx, p, d_in, n, d_out, cap, d_bits, s); });
+    });
 }
 
-extern "C" mi_status mi_deflate_h_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_stream, uint64_t stream_bytes,
-                                         const uint64_t *h_block_bits, uint8_t *h_out, uint64_t n)
+extern "C" mi_status mi_deflate_z_encode(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, const uint8_t *h_in, uint64_t n,
+                                         uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, uint64_t *h_out_bytes)
+{
+    if (!ctx || !p || !h_out || !h_block_bits || (n && !h_in)) return MI_ERR_ARG;
+    return host_encode_with_retry(ctx, [&]() -> mi_status {
+        mi_status st = defz_check(p, container);
+        if (st) return st;
+        const uint64_t bound = mi_deflate_z_bound_bytes(n, p, container);
+        if (cap_bytes < bound) return MI_ERR_CAPACITY;
+        return block_encode_once(ctx, h_in, n, (n + p->block - 1) / p->block, bound, OUT_BYTES_WORD, h_out, cap_bytes, h_block_bits, h_out_bytes,
+            [&](uint8_t *d_in, uint8_t *d_out, uint64_t cap, uint64_t *d_bits, uint64_t *d_out_bytes, hipStream_t s) {
+                return mi_deflate_z_encode_dev(ctx, p, container, d_in, n, d_out, cap, d_bits, d_out_bytes, s); });
+    });
+}
+
+extern "C" mi_status mi_bgzf_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n, uint8_t *h_out,
+                                    uint64_t cap_bytes, uint64_t *h_member_bits, uint64_t *h_out_bytes)
+{
+    if (!ctx || !p || !h_out || !h_member_bits || (n && !h_in)) return MI_ERR_ARG;
+    return host_encode_with_retry(ctx, [&]() -> mi_status {
+        mi_status st = defz_check(p, MI_CONTAINER_RAW);
+        if (st) return st;
+        if (p->block > MI_BGZF_MAX_BLOCK) return MI_ERR_ARG;
+        const uint64_t bound = mi_bgzf_bound_bytes(n, p);
+        if (cap_bytes < bound) return MI_ERR_CAPACITY;
+        return block_encode_once(ctx, h_in, n, (n + p->block - 1) / p->block, bound, OUT_BYTES_WORD, h_out, cap_bytes, h_member_bits, h_out_bytes,
+            [&](uint8_t *d_in, uint8_t *d_out, uint64_t cap, uint64_t *d_bits, uint64_t *d_out_bytes, hipStream_t s) {
+                return mi_bgzf_encode_dev(ctx, p, d_in, n, d_out, cap, d_bits, d_out_bytes, s); });
+    });
+}
+
+// tokens (mode_h 0) and mode H (1): the table indexes the stream, so it is checked before anything is copied or launched
+static mi_status block_decode_host(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_stream, uint64_t stream_bytes,
+                                   const uint64_t *h_block_bits, uint8_t *h_out, uint64_t n)
 {
     if (!ctx || !p || !h_stream || !h_block_bits || (n && !h_out) || !p->block) return MI_ERR_ARG;
     if (n == 0) return MI_OK;
     hipStream_t s = mi_host_stream(ctx);
     const uint64_t nblocks = (n + p->block - 1) / p->block;
-    mi_status st = mi_validate_block_table(h_block_bits, nblocks, stream_bytes, 32u);
+    mi_status st = mi_validate_block_table(h_block_bits, nblocks, stream_bytes, mode_h ? 32u : p->deflate ? 8u : 1u);
     if (st) return st;
     {
         bool done = false;
-        st = mi_decode_host_pipelined(ctx, p, 1, h_stream, stream_bytes, h_block_bits, h_out, n, &done);
+        st = mi_decode_host_pipelined(ctx, p, mode_h, h_stream, stream_bytes, h_block_bits, h_out, n, &done);
         if (st || done) return st;
     }
     DevBuf st_, bits, out;
@@ -397,9 +474,41 @@ extern "C" mi_status mi_deflate_h_decode(mi_ctx *ctx, const mi_lz_params *p, con
     MI_HIP(ctx, hipMemsetAsync(st_.as<uint8_t>() + stream_bytes, 0, 64, s));
     MI_HIP(ctx, hipMemcpyAsync(st_.p, h_stream, stream_bytes, hipMemcpyHostToDevice, s));
     MI_HIP(ctx, hipMemcpyAsync(bits.p, h_block_bits, (nblocks + 1) * 8, hipMemcpyHostToDevice, s));
-    st = mi_deflate_h_decode_dev(ctx, p, st_.as<uint8_t>(), stream_bytes, bits.as<uint64_t>(), out.as<uint8_t>(), n, s);
+    st = mode_h ? mi_deflate_h_decode_dev(ctx, p, st_.as<uint8_t>(), stream_bytes, bits.as<uint64_t>(), out.as<uint8_t>(), n, s)
+                : mi_lz_decode_dev(ctx, p, st_.as<uint8_t>(), stream_bytes, bits.as<uint64_t>(), out.as<uint8_t>(), n, s);
     if (st) return st;
     MI_HIP(ctx, hipMemcpy(h_out, out.p, n, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" mi_status mi_lz_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_stream, uint64_t stream_bytes,
+                                  const uint64_t *h_block_bits, uint8_t *h_out, uint64_t n)
+{
+    return block_decode_host(ctx, p, 0, h_stream, stream_bytes, h_block_bits, h_out, n);
+}
+
+extern "C" mi_status mi_deflate_h_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_stream, uint64_t stream_bytes,
+                                         const uint64_t *h_block_bits, uint8_t *h_out, uint64_t n)
+{
+    return block_decode_host(ctx, p, 1, h_stream, stream_bytes, h_block_bits, h_out, n);
+}
+
+// standard DEFLATE from a table of restart points (no tail memset, an empty output is a valid call: not block_decode_host)
+extern "C" mi_status mi_inflate(mi_ctx *ctx, uint32_t container, uint32_t block, const uint8_t *h_stream, uint64_t stream_bytes,
+                                const uint64_t *h_seg_bits, uint8_t *h_out, uint64_t n, uint32_t flags)
+{
+    if (!ctx || !h_stream || !h_seg_bits || (n && !h_out) || block == 0u) return MI_ERR_ARG;
+    const uint64_t nseg = (n + block - 1) / block;
+    mi_status st = mi_validate_block_table(h_seg_bits, nseg, stream_bytes, 8u);
+    if (st) return st;
+    hipStream_t s = mi_host_stream(ctx);
+    DevBuf st_, bits, out;
+    if (!st_.alloc(stream_bytes + 64) || !bits.alloc((nseg + 1) * 8) || !out.alloc(n + 16)) return MI_ERR_NOMEM;
+    if (stream_bytes) MI_HIP(ctx, hipMemcpyAsync(st_.p, h_stream, stream_bytes, hipMemcpyHostToDevice, s));
+    MI_HIP(ctx, hipMemcpyAsync(bits.p, h_seg_bits, (nseg + 1) * 8, hipMemcpyHostToDevice, s));
+    st = mi_inflate_dev(ctx, container, block, st_.as<uint8_t>(), stream_bytes, bits.as<uint64_t>(), out.as<uint8_t>(), n, flags, s);
+    if (st) return st;
+    if (n) MI_HIP(ctx, hipMemcpy(h_out, out.p, n, hipMemcpyDeviceToHost));
     return MI_OK;
 }
 
@@ -439,5 +548,249 @@ extern "C" mi_status mi_fse_decode(mi_ctx *ctx, const mi_fse_params *p, const ui
     st = mi_fse_decode_dev(ctx, p, in.as<uint8_t>(), bytes, offs.as<uint64_t>(), out.as<uint8_t>(), n, s);
     if (st) return st;
     MI_HIP(ctx, hipMemcpy(h_out, out.p, n, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The whole-buffer lz77 forms of the drop-in (lz77_compress_old and the decoder of what it writes): on the NULL stream, with
+// blocking copies and a device-wide synchronise, as they always were.
+// ---------------------------------------------------------------------------------------------------------------------
+// h_out holds mi_lz77_old_bound_bytes(n) bytes
+extern "C" mi_status mi_lz77_old_encode(mi_ctx *ctx, uint32_t wbits, uint32_t lbits, const uint8_t *h_in, uint64_t n,
+                                        uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_total_bits)
+{
+    if (!ctx || !h_out || !h_total_bits || (n && !h_in)) return MI_ERR_ARG;
+    if (cap_bytes < mi_lz77_old_bound_bytes(n)) return MI_ERR_CAPACITY;
+    const uint64_t cap = mi_lz77_old_bound_bytes(n);
+    DevBuf in, out, bits;
+    if (!in.alloc(n ? n : 1) || !out.alloc(cap) || !bits.alloc(8)) return MI_ERR_NOMEM;
+    if (n) MI_HIP(ctx, hipMemcpy(in.p, h_in, n, hipMemcpyHostToDevice));
+    mi_status st = mi_lz77_old_encode_dev(ctx, wbits, lbits, in.as<uint8_t>(), n, out.as<uint8_t>(), cap, bits.as<uint64_t>(), nullptr);
+    if (st) return st;
+    MI_HIP(ctx, hipDeviceSynchronize());
+    MI_HIP(ctx, hipMemcpy(h_total_bits, bits.p, 8, hipMemcpyDeviceToHost));
+    MI_HIP(ctx, hipMemcpy(h_out, out.p, (size_t)(*h_total_bits / 8 + 1), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+extern "C" mi_status mi_lz77_whole_decode(mi_ctx *ctx, uint32_t wbits, uint32_t lbits, const uint8_t *h_stream, uint64_t stream_bytes,
+                                          uint64_t total_bits, uint8_t *h_out, uint64_t n)
+{
+    if (!ctx || !h_stream || (n && !h_out)) return MI_ERR_ARG;
+    if (n == 0) return MI_OK;
+    const uint64_t sb = (stream_bytes + 3) & ~3ull;
+    DevBuf st_, out;
+    if (!st_.alloc(sb + 8) || !out.alloc(n)) return MI_ERR_NOMEM;
+    MI_HIP(ctx, hipMemset(st_.p, 0, sb + 8));
+    MI_HIP(ctx, hipMemcpy(st_.p, h_stream, stream_bytes, hipMemcpyHostToDevice));
+    mi_status st = mi_lz77_whole_decode_dev(ctx, wbits, lbits, st_.as<uint8_t>(), sb, total_bits, out.as<uint8_t>(), n, nullptr);
+    if (st) return st;
+    MI_HIP(ctx, hipMemcpy(h_out, out.p, n, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The batches: arrays of host pointers.  The items are packed into one device buffer (each at a 16-byte boundary), the
+// outputs likewise by their capacities; copy up, run the batch, copy down what came out MI_OK.
+// ---------------------------------------------------------------------------------------------------------------------
+// The caller's arrays and the per-item limit of the device form.  An item the device answers with MI_ERR_ARG takes no room
+// in the packed buffers: its (bad) pointer and size go up as they are.
+struct BatchItems {
+    uint64_t count; const void *const *in; const uint64_t *in_bytes; void *const *out; const uint64_t *out_cap; uint64_t limit;
+    bool in_ok(uint64_t i) const { return in_bytes[i] <= limit && (in[i] || !in_bytes[i]); }
+    bool out_ok(uint64_t i) const { return out_cap[i] <= limit && (out[i] || !out_cap[i]); }
+};
+
+// call(d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, s): the *_dev call.  Without b.out or b.out_cap nothing is
+// staged for the outputs and d_out, d_out_cap are NULL (the size-only mode of the inflater).
+template <class Call>
+static mi_status batch_host_once(mi_ctx *ctx, const BatchItems &b, uint64_t *h_out_bytes, uint32_t *h_status, Call call)
+{
+    const uint64_t count = b.count;
+    const bool size_only = !b.out || !b.out_cap;
+    uint64_t in_total = 0, out_total = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        if (b.in_ok(i)) in_total += mi_align_up(b.in_bytes[i], 16);
+        if (!size_only && b.out_ok(i)) out_total += mi_align_up(b.out_cap[i], 16);
+    }
+    hipStream_t s = mi_host_stream(ctx);
+    const size_t arr = mi_align_up((size_t)count * 8u, 256);
+    // host staging: [in ptrs | in bytes | out ptrs | out caps | out bytes | status], the packed inputs, the packed outputs
+    HostBuf h_arr, h_pack, h_res;
+    DevBuf d_arr, d_pack, d_res;
+    if (!h_arr.zalloc(6 * arr) || !h_pack.alloc(in_total + 16) || !h_res.alloc(out_total + 16)) return MI_ERR_NOMEM;
+    if (!d_arr.alloc(6 * arr) || !d_pack.alloc(in_total + 64) || !d_res.alloc(out_total + 64)) return MI_ERR_NOMEM;
+    uint8_t *ha = h_arr.as<uint8_t>(), *da = d_arr.as<uint8_t>();
+    uint64_t *p_in = (uint64_t *)ha, *p_nb = (uint64_t *)(ha + arr), *p_out = (uint64_t *)(ha + 2 * arr), *p_cap = (uint64_t *)(ha + 3 * arr);
+    uint64_t at = 0, ot = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        p_nb[i] = b.in_bytes[i];
+        if (b.in_ok(i)) {
+            p_in[i] = (uint64_t)(uintptr_t)(d_pack.as<uint8_t>() + at);
+            if (b.in_bytes[i]) memcpy(h_pack.as<uint8_t>() + at, b.in[i], b.in_bytes[i]);
+            at += mi_align_up(b.in_bytes[i], 16);
+        } else p_in[i] = b.in[i] ? (uint64_t)(uintptr_t)d_pack.p : 0u;
+        if (size_only) continue;
+        p_cap[i] = b.out_cap[i];
+        if (b.out_ok(i)) { p_out[i] = (uint64_t)(uintptr_t)(d_res.as<uint8_t>() + ot); ot += mi_align_up(b.out_cap[i], 16); }
+        else p_out[i] = b.out[i] ? (uint64_t)(uintptr_t)d_res.p : 0u;
+    }
+    MI_HIP(ctx, hipMemcpyAsync(da, ha, 4 * arr, hipMemcpyHostToDevice, s));
+    if (in_total) MI_HIP(ctx, hipMemcpyAsync(d_pack.p, h_pack.p, in_total, hipMemcpyHostToDevice, s));
+    mi_status st = call((const void *const *)da, (const uint64_t *)(da + arr), size_only ? nullptr : (void *const *)(da + 2 * arr),
+                        size_only ? nullptr : (const uint64_t *)(da + 3 * arr), (uint64_t *)(da + 4 * arr), (uint32_t *)(da + 5 * arr), s);
+    if (st) return st;
+    MI_HIP(ctx, hipMemcpyAsync(ha + 4 * arr, da + 4 * arr, 2 * arr, hipMemcpyDeviceToHost, s));
+    if (out_total) MI_HIP(ctx, hipMemcpyAsync(h_res.p, d_res.p, out_total, hipMemcpyDeviceToHost, s));
+    MI_HIP(ctx, hipStreamSynchronize(s));
+    const uint64_t *r_nb = (const uint64_t *)(ha + 4 * arr);
+    const uint32_t *r_st = (const uint32_t *)(ha + 5 * arr);
+    ot = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        h_out_bytes[i] = r_nb[i];
+        h_status[i] = r_st[i];
+        if (size_only || !b.out_ok(i)) continue;
+        if (r_st[i] == MI_OK && r_nb[i]) memcpy(b.out[i], h_res.as<uint8_t>() + ot, r_nb[i]);
+        ot += mi_align_up(b.out_cap[i], 16);
+    }
+    return MI_OK;
+}
+
+// inflate, or only size (without h_out / h_out_cap)
+extern "C" mi_status mi_inflate_batch(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *h_in,
+                                      const uint64_t *h_in_bytes, void *const *h_out, const uint64_t *h_out_cap,
+                                      uint64_t *h_out_bytes, uint32_t *h_status, uint32_t flags)
+{
+    if (!ctx || container > MI_CONTAINER_GZIP || (flags & ~MI_INFLATE_NO_CHECKSUM) || count > 0x7FFFFFFFull) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_in || !h_in_bytes || !h_out_bytes || !h_status) return MI_ERR_ARG;
+    const BatchItems b{count, h_in, h_in_bytes, h_out, h_out_cap, INFB_MAX_BYTES};
+    return batch_host_once(ctx, b, h_out_bytes, h_status,
+        [&](const void *const *d_in, const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+            uint32_t *d_status, hipStream_t s) {
+            return d_out ? mi_inflate_batch_dev(ctx, container, count, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, nullptr, flags, s)
+                         : mi_inflate_batch_size_dev(ctx, container, count, d_in, d_in_bytes, d_out_bytes, d_status, nullptr, flags, s); });
+}
+
+extern "C" mi_status mi_deflate_batch(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
+                                      const void *const *h_in, const uint64_t *h_in_bytes,
+                                      void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status)
+{
+    if (!ctx) return MI_ERR_ARG;
+    mi_status st = defz_check(p, container);
+    if (st) return st;
+    if (count > DFB_MAX_BYTES) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_in || !h_in_bytes || !h_out || !h_out_cap || !h_out_bytes || !h_status) return MI_ERR_ARG;
+    const BatchItems b{count, h_in, h_in_bytes, h_out, h_out_cap, DFB_MAX_BYTES};
+    return host_encode_with_retry(ctx, [&]() -> mi_status {
+        uint64_t max_blocks = 0;                                           // the launch bound: the blocks of the items that go up
+        for (uint64_t i = 0; i < count; ++i)
+            if (b.in_ok(i)) max_blocks += (h_in_bytes[i] + p->block - 1) / p->block;
+        if (max_blocks > DFB_MAX_BYTES) return MI_ERR_ARG;
+        return batch_host_once(ctx, b, h_out_bytes, h_status,
+            [&](const void *const *d_in, const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                uint32_t *d_status, hipStream_t s) {
+                return mi_deflate_batch_dev(ctx, p, container, count, d_in, d_in_bytes, max_blocks, d_out, d_out_cap, d_out_bytes, d_status, nullptr, s); });
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// BGZF read from host bytes: the stream goes up and is indexed on the device in two steps — count the members (and the bytes
+// they inflate to), then, with a table of that size, list them.
+// ---------------------------------------------------------------------------------------------------------------------
+struct BgzfIndexed { DevBuf stream, count, members; uint64_t cnt[2] = {0, 0}; };   // cnt: members, inflated bytes (count on the device)
+
+// between(): the caller's look at ix.cnt before the table is allocated (its limits, its own buffers of that size)
+template <class Between>
+static mi_status bgzf_index_host(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, BgzfIndexed &ix, Between between)
+{
+    hipStream_t s = mi_host_stream(ctx);
+    if (!ix.stream.alloc(stream_bytes + 64) || !ix.count.alloc(16)) return MI_ERR_NOMEM;
+    if (stream_bytes) MI_HIP(ctx, hipMemcpyAsync(ix.stream.p, h_stream, stream_bytes, hipMemcpyHostToDevice, s));
+    mi_status st = mi_bgzf_index_dev(ctx, ix.stream.as<uint8_t>(), stream_bytes, nullptr, 0, ix.count.as<uint64_t>(), s);
+    if (st) return st;
+    MI_HIP(ctx, hipMemcpy(ix.cnt, ix.count.p, 16, hipMemcpyDeviceToHost));
+    st = between();
+    if (st) return st;
+    if (!ix.members.alloc((ix.cnt[0] + 1) * 16)) return MI_ERR_NOMEM;
+    return mi_bgzf_index_dev(ctx, ix.stream.as<uint8_t>(), stream_bytes, ix.members.as<uint64_t>(), ix.cnt[0], ix.count.as<uint64_t>(), s);
+}
+
+// copy in, index, inflate everything, copy out
+extern "C" mi_status mi_bgzf_inflate(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint8_t *h_out, uint64_t out_cap,
+                                     uint64_t *h_out_bytes, uint32_t flags)
+{
+    if (!ctx || (stream_bytes && !h_stream) || (out_cap && !h_out)) return MI_ERR_ARG;
+    if (flags & ~MI_INFLATE_NO_CHECKSUM) return MI_ERR_ARG;
+    hipStream_t s = mi_host_stream(ctx);
+    BgzfIndexed ix;
+    DevBuf out;
+    mi_status st = bgzf_index_host(ctx, h_stream, stream_bytes, ix, [&]() -> mi_status {
+        if (ix.cnt[1] > out_cap) return MI_ERR_CAPACITY;
+        return out.alloc(ix.cnt[1] + 16) ? MI_OK : MI_ERR_NOMEM;
+    });
+    if (st) return st;
+    st = mi_bgzf_inflate_dev(ctx, ix.stream.as<uint8_t>(), stream_bytes, ix.members.as<uint64_t>(), 0, ix.cnt[0], out.as<uint8_t>(),
+                             ix.cnt[1], flags, s);
+    if (st) return st;
+    if (ix.cnt[1]) MI_HIP(ctx, hipMemcpy(h_out, out.p, ix.cnt[1], hipMemcpyDeviceToHost));
+    if (h_out_bytes) *h_out_bytes = ix.cnt[1];
+    return MI_OK;
+}
+
+// copy up, index, read, copy down.  The bound on the pieces comes from the table itself: the members, empty ones included,
+// between the first one that holds a byte of the range and the last.
+extern "C" mi_status mi_bgzf_read_ranges(mi_ctx *ctx, const uint8_t *h_stream, uint64_t stream_bytes, uint64_t count,
+                                         const uint64_t *h_off, const uint64_t *h_len, uint8_t *h_out, const uint64_t *h_out_off,
+                                         uint64_t out_bytes, uint64_t *h_got, uint32_t *h_status, uint32_t flags)
+{
+    if (!ctx || (stream_bytes && !h_stream) || (out_bytes && !h_out)) return MI_ERR_ARG;
+    if ((flags & ~MI_INFLATE_NO_CHECKSUM) || count > BGZR_MAX / 2u) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_off || !h_len || !h_out_off || !h_got || !h_status) return MI_ERR_ARG;
+    hipStream_t s = mi_host_stream(ctx);
+    const size_t arr = mi_align_up((size_t)count * 8u, 256);           // [off | len | out off | got | status]
+    HostBuf h_members;
+    DevBuf d_arr, d_out;
+    BgzfIndexed ix;
+    if (!d_arr.alloc(5 * arr) || !d_out.alloc(out_bytes + 16)) return MI_ERR_NOMEM;
+    mi_status st = bgzf_index_host(ctx, h_stream, stream_bytes, ix, [&]() -> mi_status {
+        if (ix.cnt[0] > BGZR_MAX) return MI_ERR_ARG;
+        return h_members.alloc((ix.cnt[0] + 1) * 16) ? MI_OK : MI_ERR_NOMEM;
+    });
+    if (st) return st;
+    MI_HIP(ctx, hipMemcpy(h_members.p, ix.members.p, (ix.cnt[0] + 1) * 16, hipMemcpyDeviceToHost));
+    uint64_t max_pieces = 0;
+    {
+        // (the index's own table: its output offsets do not decrease)
+        const uint64_t nm = ix.cnt[0], total = ix.cnt[1];
+        auto o = [&](uint64_t m) { return h_members.as<uint64_t>()[2 * m + 1]; };
+        for (uint64_t i = 0; i < count; ++i) {
+            const uint64_t a = h_off[i], len = h_len[i];
+            if (!len || a >= total) continue;
+            const uint64_t b = len < total - a ? a + len : total;
+            uint64_t lo = 0, hi = nm;                                   // the first member that ends behind a
+            while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (o(mid + 1) > a) hi = mid; else lo = mid + 1; }
+            const uint64_t m0 = lo;
+            hi = nm;                                                    // the first member at or behind m0 that starts at or behind b
+            while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (o(mid) >= b) hi = mid; else lo = mid + 1; }
+            max_pieces += lo - m0;
+        }
+        if (max_pieces > BGZR_MAX) return MI_ERR_ARG;
+    }
+    uint8_t *da = d_arr.as<uint8_t>();
+    MI_HIP(ctx, hipMemcpyAsync(da, h_off, count * 8, hipMemcpyHostToDevice, s));
+    MI_HIP(ctx, hipMemcpyAsync(da + arr, h_len, count * 8, hipMemcpyHostToDevice, s));
+    MI_HIP(ctx, hipMemcpyAsync(da + 2 * arr, h_out_off, count * 8, hipMemcpyHostToDevice, s));
+    if (out_bytes) MI_HIP(ctx, hipMemcpyAsync(d_out.p, h_out, out_bytes, hipMemcpyHostToDevice, s));   // what lies between the slots stays
+    st = mi_bgzf_read_ranges_dev(ctx, ix.stream.as<uint8_t>(), stream_bytes, ix.members.as<uint64_t>(), ix.cnt[0], count, (const uint64_t *)da,
+                                 (const uint64_t *)(da + arr), d_out.as<uint8_t>(), (const uint64_t *)(da + 2 * arr), out_bytes, max_pieces,
+                                 (uint64_t *)(da + 3 * arr), (uint32_t *)(da + 4 * arr), nullptr, flags, s);
+    if (st) return st;
+    MI_HIP(ctx, hipMemcpyAsync(h_got, da + 3 * arr, count * 8, hipMemcpyDeviceToHost, s));
+    MI_HIP(ctx, hipMemcpyAsync(h_status, da + 4 * arr, count * 4, hipMemcpyDeviceToHost, s));
+    if (out_bytes) MI_HIP(ctx, hipMemcpyAsync(h_out, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+    MI_HIP(ctx, hipStreamSynchronize(s));
     return MI_OK;
 }

@@ -13,6 +13,7 @@
 // bit-offset computation into a dot product with the code lengths instead of a third pass.
 #include "common.h"
 #include "heap_cells.h"
+#include "internal.h"               // huff_ws_bytes
 #include <stddef.h>
 
 #define HUFF_TILE      32768u          // input bytes per workgroup
@@ -335,6 +336,13 @@ void k_huff_encode(const uint8_t *__restrict__ in, uint64_t n, const uint32_t *_
 // ---------------------------------------------------------------------------------------------
 static inline uint64_t huff_ntiles(uint64_t n) { return (n + HUFF_TILE - 1) / HUFF_TILE; }
 
+// workspace of mi_huffman_encode_dev over n bytes (host_api.hip reserves it before it queues anything)
+size_t huff_ws_bytes(uint64_t n)
+{
+    const uint64_t ntiles = huff_ntiles(n);
+    return 256 * 4 + 256 * 4 + 256 + ntiles * 1024 + (ntiles + 1) * 8 * 2 + 4096;
+}
+
 extern "C" mi_status mi_huffman_encode_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_words,
                                            uint64_t cap_words, mi_huffman_info *d_info, mi_huffman_tree *d_tree,
                                            uint64_t *d_tile_off, void *stream)
@@ -343,7 +351,7 @@ extern "C" mi_status mi_huffman_encode_dev(mi_ctx *ctx, const uint8_t *d_in, uin
     if (((uintptr_t)d_in & 15) != 0) return MI_ERR_ARG;        // 16-B loads
     hipStream_t s = (hipStream_t)stream;   // NULL = HIP's default stream
     const uint64_t ntiles = huff_ntiles(n);
-    size_t need = 256 * 4 + 256 * 4 + 256 + ntiles * 1024 + (ntiles + 1) * 8 * 2 + 4096;
+    const size_t need = huff_ws_bytes(n);
     if (need > ctx->ws_bytes) { mi_status st = mi_ws_reserve(ctx, need); if (st) return st; }
     mi_carver cv(ctx->ws);
     uint32_t *hist = cv.take<uint32_t>(256);
@@ -462,39 +470,6 @@ extern "C" mi_status mi_huffman_encode_with_tree_dev(mi_ctx *ctx, const uint8_t 
     MI_HIP(ctx, hipGetLastError());
     return MI_OK;
 }
-
-extern "C" mi_status mi_huffman_encode(mi_ctx *ctx, const uint8_t *h_in, uint64_t n, uint32_t *h_words,
-                                       uint64_t cap_words, mi_huffman_info *h_info, mi_huffman_tree *h_tree)
-{
-    if (!ctx || !h_words || !h_info || (n && !h_in)) return MI_ERR_ARG;
-    hipStream_t s = mi_host_stream(ctx);
-    uint8_t *d_in = nullptr; uint32_t *d_words = nullptr; mi_huffman_info *d_info = nullptr; mi_huffman_tree *d_tree = nullptr;
-    mi_status st = MI_OK;
-    // reserve the kernels' workspace first: growing it later would synchronise mid-sequence
-    {
-        const uint64_t ntiles = huff_ntiles(n);
-        st = mi_ws_reserve(ctx, 256 * 4 + 256 * 4 + 256 + ntiles * 1024 + (ntiles + 1) * 8 * 2 + 4096);
-        if (st) return st;
-    }
-    if (hipMalloc(&d_in, n + 16) != hipSuccess || hipMalloc(&d_words, cap_words * 4) != hipSuccess ||
-        hipMalloc(&d_info, sizeof(mi_huffman_info)) != hipSuccess || hipMalloc(&d_tree, sizeof(mi_huffman_tree)) != hipSuccess) {
-        st = MI_ERR_NOMEM;
-    }
-    if (st == MI_OK && n && hipMemcpyAsync(d_in, h_in, n, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) st = mi_huffman_encode_dev(ctx, d_in, n, d_words, cap_words, d_info, d_tree, nullptr, s);
-    if (st == MI_OK && hipMemcpyAsync(h_info, d_info, sizeof(*h_info), hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && h_tree && hipMemcpy(h_tree, d_tree, sizeof(*h_tree), hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && h_info->status != MI_OK) st = (mi_status)h_info->status;
-    if (st == MI_OK) {
-        uint64_t nw = (h_info->total_bits + 31) >> 5;
-        if (nw > cap_words) st = MI_ERR_CAPACITY;
-        else if (nw && hipMemcpy(h_words, d_words, nw * 4, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    }
-    (void)hipFree(d_in); (void)hipFree(d_words); (void)hipFree(d_info); (void)hipFree(d_tree);
-    return st;
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // decode (replaces huffman_decompress, huffman.c:330-364; the 12-bit lookup table is what the

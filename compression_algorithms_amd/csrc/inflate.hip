@@ -175,24 +175,3 @@ extern "C" mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t bl
     MI_HIP(ctx, hipStreamSynchronize(s));
     return h_err ? MI_ERR_CORRUPT : MI_OK;
 }
-
-// host buffers: the table is checked before anything is copied; copy in, decode, copy out
-extern "C" mi_status mi_inflate(mi_ctx *ctx, uint32_t container, uint32_t block, const uint8_t *h_stream, uint64_t stream_bytes,
-                                const uint64_t *h_seg_bits, uint8_t *h_out, uint64_t n, uint32_t flags)
-{
-    if (!ctx || !h_stream || !h_seg_bits || (n && !h_out) || block == 0u) return MI_ERR_ARG;
-    const uint64_t nseg = (n + block - 1) / block;
-    mi_status st = mi_validate_block_table(h_seg_bits, nseg, stream_bytes, 8u);
-    if (st) return st;
-    hipStream_t s = mi_host_stream(ctx);
-    uint8_t *d_stream = nullptr, *d_out = nullptr; uint64_t *d_bits = nullptr;
-    if (hipMalloc(&d_stream, stream_bytes + 64) != hipSuccess || hipMalloc(&d_bits, (nseg + 1) * 8) != hipSuccess ||
-        hipMalloc(&d_out, n + 16) != hipSuccess) st = MI_ERR_NOMEM;
-    if (st == MI_OK && stream_bytes && hipMemcpyAsync(d_stream, h_stream, stream_bytes, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipMemcpyAsync(d_bits, h_seg_bits, (nseg + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) st = mi_inflate_dev(ctx, container, block, d_stream, stream_bytes, d_bits, d_out, n, flags, s);
-    if (st == MI_OK && n && hipMemcpy(h_out, d_out, n, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_ERR_HIP && !ctx->last_hip) ctx->last_hip = (int)hipGetLastError();
-    (void)hipFree(d_stream); (void)hipFree(d_bits); (void)hipFree(d_out);
-    return st;
-}

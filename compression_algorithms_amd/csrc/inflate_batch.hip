@@ -25,7 +25,6 @@
 
 #define INFB_CLASSES   33u                     // size classes: 0 (empty), then 1 + the position of the leading one, capped
 #define INFB_WS_HEAD   512u                    // bytes in front of `order`: u32 hist[64], cursor[64]
-#define INFB_MAX_BYTES 0x7FFFFFFFull           // per item, compressed and inflated: positions inside an item are 32-bit
 
 struct InfBatch {
     const void *const *in; const uint64_t *in_bytes;
@@ -215,75 +214,4 @@ extern "C" mi_status mi_inflate_batch_size_dev(mi_ctx *ctx, uint32_t container, 
 {
     return batch_launch(ctx, container, count, d_in, d_in_bytes, nullptr, nullptr, d_out_bytes, d_status, d_failed, flags,
                         (hipStream_t)stream, true);
-}
-
-// host buffers: the items packed into one device buffer (each at a 16-byte boundary), the outputs likewise by their
-// capacities; copy up, inflate (or only size, without h_out / h_out_cap), copy down what came out MI_OK
-extern "C" mi_status mi_inflate_batch(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *h_in,
-                                      const uint64_t *h_in_bytes, void *const *h_out, const uint64_t *h_out_cap,
-                                      uint64_t *h_out_bytes, uint32_t *h_status, uint32_t flags)
-{
-    if (!ctx || container > MI_CONTAINER_GZIP || (flags & ~MI_INFLATE_NO_CHECKSUM) || count > 0x7FFFFFFFull) return MI_ERR_ARG;
-    if (count == 0) return MI_OK;
-    if (!h_in || !h_in_bytes || !h_out_bytes || !h_status) return MI_ERR_ARG;
-    const bool size_only = !h_out || !h_out_cap;
-    // an item the kernel answers with MI_ERR_ARG takes no room here: its (bad) pointer and size go up as they are
-    auto in_ok = [&](uint64_t i) { return h_in_bytes[i] <= INFB_MAX_BYTES && (h_in[i] || !h_in_bytes[i]); };
-    auto out_ok = [&](uint64_t i) { return h_out_cap[i] <= INFB_MAX_BYTES && (h_out[i] || !h_out_cap[i]); };
-    uint64_t in_total = 0, out_total = 0;
-    for (uint64_t i = 0; i < count; ++i) {
-        if (in_ok(i)) in_total += mi_align_up(h_in_bytes[i], 16);
-        if (!size_only && out_ok(i)) out_total += mi_align_up(h_out_cap[i], 16);
-    }
-    hipStream_t s = mi_host_stream(ctx);
-    mi_status st = MI_OK;
-    const size_t arr = mi_align_up((size_t)count * 8u, 256);
-    // host staging: [in ptrs | in bytes | out ptrs | out caps | out bytes | status], the packed inputs, the packed outputs
-    uint8_t *h_arr = (uint8_t *)calloc(6, arr), *h_pack = (uint8_t *)malloc(in_total + 16), *h_res = (uint8_t *)malloc(out_total + 16);
-    uint8_t *d_arr = nullptr, *d_pack = nullptr, *d_res = nullptr;
-    if (!h_arr || !h_pack || !h_res) st = MI_ERR_NOMEM;
-    if (st == MI_OK && (hipMalloc(&d_arr, 6 * arr) != hipSuccess || hipMalloc(&d_pack, in_total + 64) != hipSuccess ||
-                        hipMalloc(&d_res, out_total + 64) != hipSuccess)) st = MI_ERR_NOMEM;
-    if (st == MI_OK) {
-        uint64_t *p_in = (uint64_t *)h_arr, *p_nb = (uint64_t *)(h_arr + arr), *p_out = (uint64_t *)(h_arr + 2 * arr),
-                 *p_cap = (uint64_t *)(h_arr + 3 * arr);
-        uint64_t at = 0, ot = 0;
-        for (uint64_t i = 0; i < count; ++i) {
-            p_nb[i] = h_in_bytes[i];
-            if (in_ok(i)) {
-                p_in[i] = (uint64_t)(uintptr_t)(d_pack + at);
-                if (h_in_bytes[i]) memcpy(h_pack + at, h_in[i], h_in_bytes[i]);
-                at += mi_align_up(h_in_bytes[i], 16);
-            } else p_in[i] = h_in[i] ? (uint64_t)(uintptr_t)d_pack : 0u;
-            if (size_only) continue;
-            p_cap[i] = h_out_cap[i];
-            if (out_ok(i)) { p_out[i] = (uint64_t)(uintptr_t)(d_res + ot); ot += mi_align_up(h_out_cap[i], 16); }
-            else p_out[i] = h_out[i] ? (uint64_t)(uintptr_t)d_res : 0u;
-        }
-        if (hipMemcpyAsync(d_arr, h_arr, 4 * arr, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-        if (st == MI_OK && in_total && hipMemcpyAsync(d_pack, h_pack, in_total, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    }
-    if (st == MI_OK)
-        st = batch_launch(ctx, container, count, (const void *const *)d_arr, (const uint64_t *)(d_arr + arr),
-                          size_only ? nullptr : (void *const *)(d_arr + 2 * arr), size_only ? nullptr : (const uint64_t *)(d_arr + 3 * arr),
-                          (uint64_t *)(d_arr + 4 * arr), (uint32_t *)(d_arr + 5 * arr), nullptr, flags, s, size_only);
-    if (st == MI_OK && hipMemcpyAsync(h_arr + 4 * arr, d_arr + 4 * arr, 2 * arr, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && out_total && hipMemcpyAsync(h_res, d_res, out_total, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) {
-        const uint64_t *r_nb = (const uint64_t *)(h_arr + 4 * arr);
-        const uint32_t *r_st = (const uint32_t *)(h_arr + 5 * arr);
-        uint64_t ot = 0;
-        for (uint64_t i = 0; i < count; ++i) {
-            h_out_bytes[i] = r_nb[i];
-            h_status[i] = r_st[i];
-            if (size_only || !out_ok(i)) continue;
-            if (r_st[i] == MI_OK && r_nb[i]) memcpy(h_out[i], h_res + ot, r_nb[i]);
-            ot += mi_align_up(h_out_cap[i], 16);
-        }
-    }
-    if (st == MI_ERR_HIP && !ctx->last_hip) ctx->last_hip = (int)hipGetLastError();
-    (void)hipFree(d_arr); (void)hipFree(d_pack); (void)hipFree(d_res);
-    free(h_arr); free(h_pack); free(h_res);
-    return st;
 }

@@ -1,10 +1,14 @@
-// internal.h — every function one .hip file of libmi_codec.so defines and another calls, declared ONCE, by defining file (ctx.hip's
-// are in common.h beside mi_ctx, the public extern "C" ones in include/mi_codec.h).  Callers and definers include it.  The library
-// links -shared, which accepts undefined symbols, and a definition that differs from its declaration is an overload to C++: a
-// declaration that drifts shows as ONE undefined symbol the first time the library is loaded, whichever caller runs.
+// internal.h — every function and limit one .hip file of libmi_codec.so defines and another uses, declared ONCE, by defining file
+// (ctx.hip's are in common.h beside mi_ctx, the public extern "C" ones in include/mi_codec.h).  Users and definers include it.
+// host_api.hip, the home of every host-buffer entry point, has no section: nothing it defines is called from another file.  The
+// library links -shared, which accepts undefined symbols, and a definition that differs from its declaration is an overload to
+// C++: a declaration that drifts shows as ONE undefined symbol the first time the library is loaded, whichever caller runs.
 #pragma once
 #include "lz_common.h"               // LzP, LzScratch, LzwScratch
 #include "lz2.h"                     // Lz2Scratch
+
+// ---- huffman.hip: the workspace of mi_huffman_encode_dev over n bytes
+size_t    huff_ws_bytes(uint64_t n);
 
 // ---- lz_find.hip: parameters, workspace and the stages of the match finder
 mi_status lz_check_params(const mi_lz_params *p);
@@ -79,11 +83,15 @@ struct DfbCall {
     const void *const *in; const uint64_t *in_bytes; void *const *out; const uint64_t *out_cap;
     uint64_t *out_bytes; uint32_t *status, *failed;
 };
+#define DFB_MAX_BYTES 0x7FFFFFFFull            // per item and per count: block numbers and positions inside an item are 32-bit
 size_t    dfb_ws_bytes(const DfbCall &b);
 mi_status dfb_begin(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s, const uint8_t **desc);
 void      dfb_launch_place(const DfbCall &b, void *ws, const uint32_t *slots, const uint64_t *block_bits, uint64_t b0, uint32_t nb,
                            uint64_t seq, hipStream_t s);
 mi_status dfb_end(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s);
+
+// ---- inflate_batch.hip: the per-item limit
+#define INFB_MAX_BYTES 0x7FFFFFFFull           // per item, compressed and inflated: positions inside an item are 32-bit
 
 // ---- inflate.hip: k_inflate over segment descriptors (BGZF members) instead of a table of restart points
 struct InfSeg { uint64_t first_bit, last_bit, out_off; uint32_t out_len, crc; };   // crc: the member's trailer, for bgzf.hip
@@ -100,7 +108,5 @@ void      bgzf_launch_frame(uint32_t *slots, uint64_t *block_bits, const uint8_t
                             uint32_t nb, hipStream_t s);
 mi_status bgzf_end(mi_ctx *ctx, uint8_t *d_out, const uint64_t *d_member_bits, uint64_t nblocks, uint64_t *d_out_bytes, hipStream_t s);
 
-// ---- host_api.hip: the pipelined host-buffer encode; the one-more-try rule of the host-buffer encoders
-mi_status mi_encode_host_pipelined(mi_ctx *ctx, const mi_lz_params *p, int mode_h, const uint8_t *h_in, uint64_t n,
-                                   uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits, bool *done);
-mi_status mi_encode_again_if_unstable(mi_ctx *ctx, uint32_t seen_before, mi_status st, mi_status (*again)(void *), void *arg);
+// ---- bgzf_ranges.hip: the per-call limit
+#define BGZR_MAX     0x7FFFFFFFull             // ranges, members and pieces per call: their numbers are 32-bit

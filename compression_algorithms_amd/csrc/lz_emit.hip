@@ -792,49 +792,6 @@ extern "C" mi_status mi_bgzf_encode_dev(mi_ctx *ctx, const mi_lz_params *p, cons
     return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_member_bits, stream, 2, &z);
 }
 
-static mi_status lz_encode_host_once(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
-                                     uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits);
-struct LzHostEncArgs { mi_ctx *ctx; const mi_lz_params *p; const uint8_t *h_in; uint64_t n; uint8_t *h_out; uint64_t cap; uint64_t *bits; };
-
-extern "C" mi_status mi_lz_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
-                                  uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits)
-{
-    if (!ctx || !h_out || !h_block_bits || (n && !h_in) || !p) return MI_ERR_ARG;
-    mi_order_poll(ctx);
-    const uint32_t seen = ctx->order_violations;
-    LzHostEncArgs a{ctx, p, h_in, n, h_out, cap_bytes, h_block_bits};
-    return mi_encode_again_if_unstable(ctx, seen, lz_encode_host_once(ctx, p, h_in, n, h_out, cap_bytes, h_block_bits),
-        [](void *v) { LzHostEncArgs *q = (LzHostEncArgs *)v; return lz_encode_host_once(q->ctx, q->p, q->h_in, q->n, q->h_out, q->cap, q->bits); }, &a);
-}
-
-static mi_status lz_encode_host_once(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
-                                     uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits)
-{
-    const uint64_t nblocks = p->block ? (n + p->block - 1) / p->block : 0;
-    const uint64_t bound = mi_lz_bound_bytes(n, p);
-    if (cap_bytes < bound) return MI_ERR_CAPACITY;
-    if (lz_check_params(p) == MI_OK && p->deflate) {       // byte tokens: chunks overlap their transfers with the encoder (host_api.hip)
-        bool done = false;
-        const mi_status ps = mi_encode_host_pipelined(ctx, p, 0, h_in, n, h_out, cap_bytes, h_block_bits, &done);
-        if (ps || done) return ps;
-    }
-    uint8_t *d_in = nullptr, *d_out = nullptr; uint64_t *d_bits = nullptr;
-    mi_status st = MI_OK;
-    hipStream_t s = mi_host_stream(ctx);
-    if (hipMalloc(&d_in, n + 64) != hipSuccess || hipMalloc(&d_out, bound + 64) != hipSuccess ||
-        hipMalloc(&d_bits, (nblocks + 1) * 8) != hipSuccess) st = MI_ERR_NOMEM;
-    if (st == MI_OK && n && hipMemcpyAsync(d_in, h_in, n, hipMemcpyHostToDevice, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) st = mi_lz_encode_dev(ctx, p, d_in, n, d_out, bound + 64, d_bits, s);
-    if (st == MI_OK && hipMemcpyAsync(h_block_bits, d_bits, (nblocks + 1) * 8, hipMemcpyDeviceToHost, s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK && hipStreamSynchronize(s) != hipSuccess) st = MI_ERR_HIP;
-    if (st == MI_OK) {
-        const uint64_t bytes = (h_block_bits[nblocks] + 7) / 8;
-        if (bytes && hipMemcpy(h_out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    }
-    (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_bits);
-    return st;
-}
-
 // launch alone: errors accumulate in *err (an mi_err_slot the caller reads once everything it launched has run)
 mi_status mi_lz_decode_launch(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_stream, uint64_t stream_bytes,
                               const uint64_t *d_block_bits, uint8_t *d_out, uint64_t n, uint32_t *err, hipStream_t s)

@@ -197,25 +197,6 @@ extern "C" mi_status mi_lz77_old_encode_dev(mi_ctx *ctx, uint32_t wbits, uint32_
     return MI_OK;
 }
 
-// host buffers (what the drop-in's lz77_compress_old calls): h_out holds mi_lz77_old_bound_bytes(n) bytes
-extern "C" mi_status mi_lz77_old_encode(mi_ctx *ctx, uint32_t wbits, uint32_t lbits, const uint8_t *h_in, uint64_t n,
-                                        uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_total_bits)
-{
-    if (!ctx || !h_out || !h_total_bits || (n && !h_in)) return MI_ERR_ARG;
-    if (cap_bytes < mi_lz77_old_bound_bytes(n)) return MI_ERR_CAPACITY;
-    const uint64_t cap = mi_lz77_old_bound_bytes(n);
-    uint8_t *d_in = nullptr, *d_out = nullptr; uint64_t *d_bits = nullptr;
-    mi_status st = MI_OK;
-    if (hipMalloc(&d_in, n ? n : 1) != hipSuccess || hipMalloc(&d_out, cap) != hipSuccess || hipMalloc(&d_bits, 8) != hipSuccess) st = MI_ERR_NOMEM;
-    if (!st && n && hipMemcpy(d_in, h_in, n, hipMemcpyHostToDevice) != hipSuccess) st = MI_ERR_HIP;
-    if (!st) st = mi_lz77_old_encode_dev(ctx, wbits, lbits, d_in, n, d_out, cap, d_bits, nullptr);
-    if (!st && hipDeviceSynchronize() != hipSuccess) st = MI_ERR_HIP;
-    if (!st && hipMemcpy(h_total_bits, d_bits, 8, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    if (!st && hipMemcpy(h_out, d_out, (size_t)(*h_total_bits / 8 + 1), hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_bits);
-    return st;
-}
-
 // Decoder of a WHOLE-BUFFER lz77 stream (one stream, no block table: what lz77_compress_old writes, and lz77_compress for a
 // buffer of one block): one wave, the block decoder of lz_decode.hip with the buffer as its only block (lz77.c:347-377).
 extern "C" mi_status mi_lz77_whole_decode_dev(mi_ctx *ctx, uint32_t wbits, uint32_t lbits, const uint8_t *d_stream, uint64_t stream_bytes,
@@ -241,21 +222,4 @@ extern "C" mi_status mi_lz77_whole_decode_dev(mi_ctx *ctx, uint32_t wbits, uint3
     MI_HIP(ctx, hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, s));
     MI_HIP(ctx, hipStreamSynchronize(s));
     return h_err ? MI_ERR_CORRUPT : MI_OK;
-}
-
-// host buffers (the drop-in's lz77_decompress for a stream lz77_compress_old wrote)
-extern "C" mi_status mi_lz77_whole_decode(mi_ctx *ctx, uint32_t wbits, uint32_t lbits, const uint8_t *h_stream, uint64_t stream_bytes,
-                                          uint64_t total_bits, uint8_t *h_out, uint64_t n)
-{
-    if (!ctx || !h_stream || (n && !h_out)) return MI_ERR_ARG;
-    if (n == 0) return MI_OK;
-    uint8_t *d_s = nullptr, *d_o = nullptr;
-    const uint64_t sb = (stream_bytes + 3) & ~3ull;
-    mi_status st = MI_OK;
-    if (hipMalloc(&d_s, sb + 8) != hipSuccess || hipMalloc(&d_o, n) != hipSuccess) st = MI_ERR_NOMEM;
-    if (!st && (hipMemset(d_s, 0, sb + 8) != hipSuccess || hipMemcpy(d_s, h_stream, stream_bytes, hipMemcpyHostToDevice) != hipSuccess)) st = MI_ERR_HIP;
-    if (!st) st = mi_lz77_whole_decode_dev(ctx, wbits, lbits, d_s, sb, total_bits, d_o, n, nullptr);
-    if (!st && hipMemcpy(h_out, d_o, n, hipMemcpyDeviceToHost) != hipSuccess) st = MI_ERR_HIP;
-    (void)hipFree(d_s); (void)hipFree(d_o);
-    return st;
 }

@@ -4,6 +4,7 @@ items, a launch bound that is too small, an item that straddles pipeline batches
 the batched inflater, and the host form."""
 import ctypes as C
 import functools
+import zlib
 
 import numpy as np
 import pytest
@@ -225,3 +226,27 @@ def test_python_round_trip_and_host_form(ctx, container):
     d2 = lz.deflate_batch((buf, offs), p, container, caps=caps, ctx=ctx)
     assert d2.failed == 1 and int(d2.status[1]) == B.CAPACITY and int(d2.out_bytes[1]) == len(oracle(items[1], 1000, container))
     assert [o.cpu().numpy().tobytes() for k, o in enumerate(d2.outputs) if k != 1] == [oracle(x, 1000, container) for k, x in enumerate(items) if k != 1]
+
+
+def test_host_form_with_mixed_verdicts(ctx):
+    """mi_deflate_batch by hand: good, a byte short, NULL with a size, empty — every item has its own verdict, the one that
+    does not fit reports the size it needs and leaves its buffer alone"""
+    p, c = lz.params("deflate"), lz.CONTAINERS["gzip"]
+    items = [B.text(1000, seed=11), B.text(65537, seed=12), b"12345", b""]
+    want = [oracle(x, 65536, "gzip") for x in items]
+    arrs = [np.frombuffer(x, dtype=np.uint8) for x in items]
+    h_in = (C.c_void_p * 4)(*[a.ctypes.data if a.size else None for a in arrs])
+    h_in[2] = None
+    h_nb = (C.c_uint64 * 4)(*[a.size for a in arrs])
+    caps = [lz.bound_bytes_z(len(x), p, c) for x in items]
+    caps[1] = len(want[1]) - 1
+    outs = [np.full(v, FILL, dtype=np.uint8) for v in caps]
+    h_out = (C.c_void_p * 4)(*[o.ctypes.data for o in outs])
+    h_cap = (C.c_uint64 * 4)(*caps)
+    sizes, status = (C.c_uint64 * 4)(), (C.c_uint32 * 4)()
+    assert ctx.L.mi_deflate_batch(ctx.h, C.byref(p), c, 4, h_in, h_nb, h_out, h_cap, sizes, status) == 0
+    assert list(status) == [B.OK, B.CAPACITY, B.ARG, B.OK]
+    assert sizes[1] == len(want[1]) and bool((outs[1] == FILL).all())
+    for k in (0, 3):
+        got = outs[k][: int(sizes[k])].tobytes()
+        assert got == want[k] and zlib.decompress(got, 31) == items[k], k

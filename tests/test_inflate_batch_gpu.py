@@ -283,6 +283,34 @@ def test_host_form_equals_zlib(container):
     assert status == [0] * len(items) and outs == [zlib.decompress(i, K.WBITS[container]) for _, i, _ in items]
 
 
+def test_host_form_with_mixed_verdicts():
+    """mi_inflate_batch by hand (lz.inflate_batch_host sizes its own outputs and cannot express a short capacity): good, a
+    byte short, truncated, NULL with a size, good — the call is MI_OK, every item has its own verdict, only the good ones are
+    written; then the size-only call on the same five"""
+    ctx = lz.default_context()
+    _, item, want = next(c for c in K.clean_items("raw") if c[0] == "text_2k")
+    n = len(want)
+    streams = [item, item, item[:-3], item, item]
+    arrs = [np.frombuffer(b, dtype=np.uint8) for b in streams]
+    h_in = (C.c_void_p * 5)(*[a.ctypes.data for a in arrs])
+    h_in[3] = None
+    h_nb = (C.c_uint64 * 5)(*[a.size for a in arrs])
+    caps = [n, n - 1, n, n, n]
+    outs = [np.full(n, PATTERN, dtype=np.uint8) for _ in range(5)]
+    h_out = (C.c_void_p * 5)(*[o.ctypes.data for o in outs])
+    h_cap = (C.c_uint64 * 5)(*caps)
+    sizes, status = (C.c_uint64 * 5)(), (C.c_uint32 * 5)()
+    assert ctx.L.mi_inflate_batch(ctx.h, CID["raw"], 5, h_in, h_nb, h_out, h_cap, sizes, status, 0) == 0
+    assert list(status) == [0, K.CAPACITY, K.CORRUPT, K.ARG, 0]
+    assert sizes[0] == n and sizes[1] == n and sizes[4] == n
+    assert outs[0].tobytes() == want == zlib.decompress(item, -15) and outs[4].tobytes() == want
+    assert bool((outs[1] == PATTERN).all()), "an item that did not fit was written"
+    sizes, status = (C.c_uint64 * 5)(), (C.c_uint32 * 5)()
+    assert ctx.L.mi_inflate_batch(ctx.h, CID["raw"], 5, h_in, h_nb, None, None, sizes, status, 0) == 0
+    assert list(status) == [0, 0, K.CORRUPT, K.ARG, 0]
+    assert sizes[0] == n and sizes[1] == n and sizes[4] == n
+
+
 # ---- 10. arguments ----------------------------------------------------------------------------------------------------
 @clean
 def test_arguments():

@@ -83,32 +83,70 @@ def test_broken_ranking_is_noticed_and_the_context_recovers(shape):
     """)
 
 
-@pytest.mark.parametrize("mode_h", [False, True])
-def test_host_entry_points_encode_again_by_themselves(mode_h):
+@pytest.mark.parametrize("form", [False, True, "z", "bgzf", "batch"])
+def test_host_entry_points_encode_again_by_themselves(form):
+    """every host-buffer encoder that goes through the one-more-try rule: tokens (False), mode H (True), mode Z, BGZF and the
+    batched deflate"""
     _run_with_broken_ranking(f"""
-        mode_h = {mode_h!r}
+        import sys
+        sys.path.insert(0, "tests")
+        import bgzf_cases
+        form = {form!r}
         ctx = Context(0)
-        p = lz.params("deflate")
         data = synth.enwik_like(5 * 65536 + 99, seed=92).numpy()
         n = len(data)
-        nblocks = (n + 65535) // 65536
-        cap = (int(ctx.L.mi_deflate_h_bound_bytes(n, C.byref(p))) if mode_h else lz.bound_bytes(n, p)) + 64
-        out = np.zeros(cap, np.uint8)
-        bits = np.zeros(nblocks + 1, np.uint64)
-        fn = ctx.L.mi_deflate_h_encode if mode_h else ctx.L.mi_lz_encode
-        rc = fn(ctx.h, C.byref(p), C.c_void_p(data.ctypes.data), C.c_uint64(n), C.c_void_p(out.ctypes.data), C.c_uint64(cap), C.c_void_p(bits.ctypes.data))
+        ptr = lambda a: C.c_void_p(a.ctypes.data)
+        if form in (False, True):
+            p = lz.params("deflate")
+            nblocks = (n + 65535) // 65536
+            cap = (int(ctx.L.mi_deflate_h_bound_bytes(n, C.byref(p))) if form else lz.bound_bytes(n, p)) + 64
+            out = np.zeros(cap, np.uint8)
+            bits = np.zeros(nblocks + 1, np.uint64)
+            fn = ctx.L.mi_deflate_h_encode if form else ctx.L.mi_lz_encode
+            rc = fn(ctx.h, C.byref(p), ptr(data), C.c_uint64(n), ptr(out), C.c_uint64(cap), ptr(bits))
+        elif form in ("z", "bgzf"):
+            p = lz.params("deflate", block=65536 if form == "z" else 65280)
+            nblocks = (n + p.block - 1) // p.block
+            cap = lz.bound_bytes_z(n, p, lz.CONTAINERS["gzip"]) if form == "z" else lz.bound_bytes_bgzf(n, p)
+            out = np.zeros(cap, np.uint8)
+            bits = np.zeros(nblocks + 1, np.uint64)
+            nb = C.c_uint64(0)
+            if form == "z":
+                rc = ctx.L.mi_deflate_z_encode(ctx.h, C.byref(p), lz.CONTAINERS["gzip"], ptr(data), n, ptr(out), cap, ptr(bits), C.byref(nb))
+            else:
+                rc = ctx.L.mi_bgzf_encode(ctx.h, C.byref(p), ptr(data), n, ptr(out), cap, ptr(bits), C.byref(nb))
+        else:
+            p = lz.params("deflate")
+            items = [data[:0], data[:65537], data[65537:]]
+            caps = [lz.bound_bytes_z(len(x), p, lz.CONTAINERS["gzip"]) for x in items]
+            outs = [np.zeros(v, np.uint8) for v in caps]
+            h_in = (C.c_void_p * 3)(*[x.ctypes.data if x.size else None for x in items])
+            h_nb = (C.c_uint64 * 3)(*[x.size for x in items])
+            h_out = (C.c_void_p * 3)(*[o.ctypes.data for o in outs])
+            h_cap = (C.c_uint64 * 3)(*caps)
+            sizes, status = (C.c_uint64 * 3)(), (C.c_uint32 * 3)()
+            rc = ctx.L.mi_deflate_batch(ctx.h, C.byref(p), lz.CONTAINERS["gzip"], 3, h_in, h_nb, h_out, h_cap, sizes, status)
         assert rc == 0
         assert ctx.order_violations() >= 1
         ctx.sync()                                            # handled inside the call: nothing left to report
-        tok, sizes = orc.deflate_stream(data, 65536, True)
-        if not mode_h:
+        if form in (False, True):
+            tok, sizes = orc.deflate_stream(data, 65536, True)
+        if form is False:
             assert np.array_equal(out[: int(bits[-1]) // 8], tok)
-        else:
+        elif form is True:
             at = 0
             for b, s in enumerate(sizes):
                 want = orc.defh_encode_block(tok[at:at + int(s)])
                 at += int(s)
                 assert np.array_equal(out[int(bits[b]) // 8:int(bits[b + 1]) // 8], want), b
+        elif form == "z":
+            assert out[: nb.value].tobytes() == bytes(orc.defz_stream(data, 65536, "gzip")[0])
+        elif form == "bgzf":
+            assert out[: nb.value].tobytes() == bgzf_cases.expected_bgzf(data)[0]
+        else:
+            assert list(status) == [0, 0, 0]
+            for k, x in enumerate(items):
+                assert outs[k][: int(sizes[k])].tobytes() == bytes(orc.defz_stream(x, 65536, "gzip")[0]), k
     """)
 
 
