@@ -84,18 +84,12 @@ mi_status mi_ctx_create(mi_ctx **out, int device)
     {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);      // lo = least urgent
-        // stage B's stream: MI_SIDE_PRIO=lo creates it at the least urgent priority (A/B: partition + find are the chain the
-        // pipeline is bound by, and the replay kernels' small waves fragment the LDS their workgroups wait for)
-        const char *sp_ = getenv("MI_SIDE_PRIO");
-        bool ok = (sp_ && sp_[0] == 'l') ? hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, lo) == hipSuccess
-                                         : hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess;
+        // stage B's stream at the default priority, the fallback chain's at the least urgent
+        bool ok = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess;
         ok = ok && hipStreamCreateWithPriority(&c->fb, hipStreamNonBlocking, lo) == hipSuccess;
         // stage C at raised priority: k_lz_parse_emit wants a whole CU's LDS and only gets one when all the workgroups of
         // k_lz2_find on it have left — first in line it spans 4.5 ms per launch instead of 6.4 and the step is 0.6 % shorter
-        // (MI_PARSE_PRIO=0: default priority, for A/B)
-        const char *pp = getenv("MI_PARSE_PRIO");
-        if (pp && pp[0] == '0') ok = ok && hipStreamCreateWithFlags(&c->parse, hipStreamNonBlocking) == hipSuccess;
-        else ok = ok && hipStreamCreateWithPriority(&c->parse, hipStreamNonBlocking, hi) == hipSuccess;
+        ok = ok && hipStreamCreateWithPriority(&c->parse, hipStreamNonBlocking, hi) == hipSuccess;
         if (!ok) { mi_ctx_destroy(c); return MI_ERR_HIP; }
     }
     for (int i = 0; i < MI_SETS; ++i) {

@@ -301,6 +301,5 @@ extern "C" mi_status mi_deflate_batch_dev(mi_ctx *ctx, const mi_lz_params *p, ui
     if (count == 0) return MI_OK;
     if (!d_in || !d_in_bytes || !d_out || !d_out_cap || !d_out_bytes || !d_status) return MI_ERR_ARG;
     const DfbCall b{container, count, max_blocks, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, d_failed};
-    const DefzCall z{container, nullptr, false, &b};
-    return lz_encode_impl(ctx, p, nullptr, 0, nullptr, 0, nullptr, stream, 2, &z);
+    return lz_encode_impl(ctx, p, nullptr, 0, nullptr, 0, nullptr, stream, LzCall{LZ_BATCH, container, nullptr, &b});
 }

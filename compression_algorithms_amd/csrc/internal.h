@@ -61,8 +61,6 @@ mi_status mi_deflate_h_decode_launch(mi_ctx *ctx, const mi_lz_params *p, const u
                                      const uint64_t *d_block_bits, uint8_t *d_out, uint64_t n, uint32_t *err, hipStream_t s);
 
 // ---- defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
-struct DfbCall;                                                        // a batch of independent items (deflate_batch.hip, below)
-struct DefzCall { uint32_t container; uint64_t *d_out_bytes; bool bgzf = false; const DfbCall *batch = nullptr; };   // bgzf: every record framed as a gzip member
 void      defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
                              uint32_t block, uint64_t b0, uint32_t nb, bool desc, hipStream_t s);     // desc: d_in is a descriptor table
 uint32_t  defz_header_bytes(uint32_t container);
@@ -74,10 +72,13 @@ mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint6
 mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
                    void *zws, uint64_t *d_out_bytes, hipStream_t s);
 
-// ---- lz_emit.hip: the encoder pipeline (modes T, H, Z, BGZF and, with z->batch, the batch); deflate_batch.hip: what a batch adds
-// to it — the descriptor table and per-block checksums in front, the placement of one pipeline batch's records, the per-item finish
+// ---- lz_emit.hip: the encoder pipeline and the form of its output (lz_emit.hip describes the five); deflate_batch.hip: what a batch
+// adds to it — the descriptor table and per-block checksums in front, the placement of one pipeline batch's records, the per-item finish
+enum LzForm { LZ_TOKENS, LZ_H, LZ_Z, LZ_BGZF, LZ_BATCH };
+struct DfbCall;
+struct LzCall { LzForm form; uint32_t container; uint64_t *d_out_bytes; const DfbCall *batch; };   // container, d_out_bytes: LZ_Z, LZ_BGZF; batch: LZ_BATCH
 mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
-                         uint64_t *d_block_bits, void *stream, int mode_h, const DefzCall *z = nullptr);
+                         uint64_t *d_block_bits, void *stream, const LzCall &c);
 struct DfbCall {
     uint32_t container; uint64_t count, max_blocks;
     const void *const *in; const uint64_t *in_bytes; void *const *out; const uint64_t *out_cap;

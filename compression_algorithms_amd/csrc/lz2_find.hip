@@ -11,10 +11,9 @@
 //                         that covers the block stops right after the sweep;
 //                       - mixed clusters of 2..7 entries are replayed one lane each, their table in two registers;
 //                       - larger mixed ones are exported on 16-byte boundaries, by size class.
-//   k_lz2_mid_direct  lane per exported cluster of 8..127 entries (64 clusters per wave, LDS regions per lane),
-//                     eight entries per load.
-//   k_lz2_lanes       the same replay in ONE launch (default; k_lz2_mid_direct with MI_LZ_LANES=0): the clusters sorted by size
-//                     (k_lz2_lane_count / k_lz2_lane_place), a wave per group of clusters of one size, regions sized by it.
+//   k_lz2_lanes       lane per exported cluster of 8..127 entries (LDS regions per lane, eight entries per load), ONE launch:
+//                     the clusters sorted by size (k_lz2_lane_count / k_lz2_lane_place), a wave per group of clusters of one
+//                     size, regions sized by it.
 //   k_lz2_big         one WAVE per exported cluster of 512..1024 entries (and of what the row replay leaves): occupancy bitmap in
 //                     registers, first fit by ballot + v_readlane, 6 bytes of LDS per entry; bound by scalar-instruction issue.
 //   k_lz2_rows        FOUR exported clusters of 128..511 entries per wave, one per 16-lane row, 256..511 first (round 4).
@@ -1020,14 +1019,6 @@ void k_lz2_rows(LzP P, Lz2Scratch sc, int cls_a, int cls_b, int cursor_slot)
     }
 }
 
-// =============================================================================================
-// lane-per-cluster replay of exported clusters of one size class [16,32) / [32,64) / [64,128):
-// 64 clusters per wave, every lane owns a private LDS region (slot -> word id, slot -> position,
-// entry -> slot, occupancy bits).  All lanes of a wave step through clusters of similar size.
-// =============================================================================================
-template <bool SMALL> struct SlotType { typedef uint8_t type; };
-template <> struct SlotType<false> { typedef uint16_t type; };
-
 // Measured alternatives (round 1, same box): staging 16 entries of all 64 clusters through LDS by coalesced loads ran
 // 14 % faster alone (7.16 vs 8.35 ms / 400 MB) but its 3x LDS footprint cost the overlapped pipeline 4 % (10.46 vs 10.88
 // GB/s) — k_lz2_find needs the whole LDS of a CU for its two workgroups; packing an entry into one 8-byte record
@@ -1041,99 +1032,14 @@ __device__ __forceinline__ uint32_t u16_of(const uint4 &v, uint32_t k)      // k
     return (uint32_t)(((k & 4u) ? hi : lo) >> ((k & 3u) * 16u)) & 0xFFFFu;
 }
 
-template <int CMAX, int LANES>
-__global__ __launch_bounds__(64)
-void k_lz2_mid_direct(LzP P, Lz2Scratch sc, int cls)
-{
-    constexpr int STRIDE = CMAX + 1;                      // odd stride: spreads the lanes over the banks
-    typedef typename SlotType<(CMAX <= 128)>::type slot_t;     // a slot number fits a byte up to 255
-    __shared__ uint32_t s_occ[LANES * STRIDE];            // slot -> word id | position << 16 of its occupant
-    __shared__ slot_t   s_slot[LANES * STRIDE];           // entry -> slot (for its eviction)
-    __shared__ uint32_t s_bits[LANES * (CMAX / 32 + 1)];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t ncl = sc.big_count[cls];
-    // persistent grid: a wave takes LANES clusters at a time until the class is done (a worst-case grid was 131 k
-    // workgroups for the 8..15 class, nearly all of them empty)
-    for (uint32_t wg = blockIdx.x; wg * (uint32_t)LANES < ncl; wg += gridDim.x) {
-    const uint32_t ci = wg * (uint32_t)LANES + lane;
-    const bool active = ci < ncl && lane < (uint32_t)LANES;
-    struct { uint32_t block, start, count, anom, limit; } d = {0u, 0u, 0u, ~0u, ~0u};
-    if (active) { const Lz2BigDesc *dp = &sc.desc[cls][ci]; d.block = dp->block; d.start = dp->start; d.count = dp->count; d.anom = dp->anom; d.limit = dp->limit; }
-    const uint32_t n = d.count, W = 1u << P.wbits;
-    // Every lane walks its own cluster, so nothing coalesces, and 2-byte loads cost a cache line each: rocprofv3 showed
-    // 1.5 GB of HBM traffic per launch against 60 MB of entries (the lines do not survive in L1 between steps).  Clusters
-    // start on 16-byte boundaries (lz2.h), so a lane fetches EIGHT entries per load and stores eight results at once.
-    const uint4 *vp = reinterpret_cast<const uint4 *>(sc.bigpos + (size_t)d.block * LZ2_BIG_STRIDE + d.start);
-    const uint4 *vr = reinterpret_cast<const uint4 *>(sc.bigrs + (size_t)d.block * LZ2_BIG_STRIDE + d.start);
-    const uint4 *vi = reinterpret_cast<const uint4 *>(sc.bigpid + (size_t)d.block * LZ2_BIG_STRIDE + d.start);
-    uint4 *vc = reinterpret_cast<uint4 *>(sc.bigcand + (size_t)d.block * LZ2_BIG_STRIDE + d.start);
-    const uint32_t lr = lane < (uint32_t)LANES ? lane : 0u;  // surplus lanes (LANES < 64) idle on region 0: n = 0
-    uint32_t *occ = s_occ + lr * STRIDE;
-    slot_t *slot = s_slot + lr * STRIDE;
-    uint32_t *bits = s_bits + lr * (CMAX / 32 + 1);
-    if (lane < (uint32_t)LANES) for (int k = 0; k < CMAX / 32 + 1; ++k) bits[k] = 0;
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-    uint4 evw = zero4;                                     // positions of entries [ev & ~7, +8): the next to retire
-    if (n) evw = vp[0];
-    uint32_t ev = 0, ev_p = evw.x & 0xFFFFu;
-    bool anom_pending = d.anom != ~0u;
-    const bool plain = d.anom == ~0u && d.limit == ~0u;    // not the cluster that covers bucket 0 / T
-    uint4 np = evw, nr = zero4, ni = zero4;                // the group after the current one is in flight
-    if (n) { nr = vr[0]; ni = vi[0]; }
-    for (uint32_t i0 = 0; i0 < (uint32_t)CMAX; i0 += 8) {
-        if (__ballot(i0 < n) == 0ull) break;                // every cluster of this wave is done
-        const uint4 cp = np, cr = nr, cid = ni;
-        if (i0 + 8 < n) { np = vp[(i0 >> 3) + 1]; nr = vr[(i0 >> 3) + 1]; ni = vi[(i0 >> 3) + 1]; }
-        uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) {
-            const uint32_t i = i0 + k;
-            if (i < n) {                                   // lanes with shorter clusters idle (same size class: < 2x)
-                const uint32_t p = u16_of(cp, k), r = u16_of(cr, k), id = u16_of(cid, k);
-                while (ev < i && ev_p + W < p) {           // FIFO retirement
-                    const uint32_t b = slot[ev];
-                    bits[b >> 5] &= ~(1u << (b & 31u));
-                    ++ev;
-                    if ((ev & 7u) == 0) evw = vp[ev >> 3];
-                    ev_p = u16_of(evw, ev & 7u);
-                }
-                if (anom_pending && p > W - 1u) { bits[d.anom >> 5] &= ~(1u << (d.anom & 31u)); anom_pending = false; }
-                uint32_t wi = r >> 5;
-                const uint32_t w0 = bits[wi];
-                uint32_t res = LZ_NONE16;
-                if (plain && ev == 0) {                    // nothing evicted yet: find() = the word's first occurrence,
-                    if (id != p) res = id;                 // which is what the word id is (k_lz2_find, the sweep)
-                } else if (id != p && ((w0 >> (r & 31u)) & 1u)) {       // (a word's first occurrence in the block finds nothing, ever)
-                    for (uint32_t b = r;; ++b) {
-                        if (b != r) {
-                            if (b == d.limit && r < d.limit) break;
-                            if (!((bits[b >> 5] >> (b & 31u)) & 1u)) break;
-                        }
-                        const uint32_t o = occ[b];
-                        if ((o & 0xFFFFu) == id) { res = o >> 16; break; }
-                    }
-                }
-                { const uint32_t v = res << ((k & 1u) * 16u); if (k < 2) o0 |= v; else if (k < 4) o1 |= v; else if (k < 6) o2 |= v; else o3 |= v; }
-                uint32_t wv = w0 | ((1u << (r & 31u)) - 1u);
-                while (wv == 0xFFFFFFFFu) wv = bits[++wi];
-                const uint32_t b = (wi << 5) + (uint32_t)__builtin_ctz(~wv);
-                bits[b >> 5] |= 1u << (b & 31u);
-                occ[b] = id | (p << 16); slot[i] = (slot_t)b;
-            }
-        }
-        if (i0 < n) vc[i0 >> 3] = make_uint4(o0, o1, o2, o3);      // pads of the last group: 0 (= skipped, lz2.h)
-    }
-    __builtin_amdgcn_wave_barrier();
-    }
-}
-
 // =============================================================================================
 // The lane classes in one launch (round 6).  The exported clusters of 8..127 entries become ONE list sorted by size, longest
 // first (a counting sort over the sizes: k_lz2_lane_count, k_lz2_lane_place); k_lz2_lanes gives a wave clusters of ONE size,
 // as many as its LDS budget holds (at most 64), every lane's region sized by that size: n + 1 occupant dwords, ceil((n + 1) / 32)
-// bitmap words, n slot bytes, rounded up to an odd number of dwords (the regions of the lanes start on different banks, as the
-// odd stride of k_lz2_mid_direct did).  No lane idles behind a longer cluster, and a wave of 64-entry clusters holds twice the
-// lanes of k_lz2_mid_direct<128, 48>.  Waves are numbered long clusters first; the dispatcher hands them out in that order.
+// bitmap words, n slot bytes (a slot number fits a byte up to 255), rounded up to an odd number of dwords: the regions of the
+// lanes start on different banks.  No lane idles behind a longer cluster, and a wave of 64-entry clusters holds twice the lanes
+// that regions sized for the whole 64..127 class would leave it.  Waves are numbered long clusters first; the dispatcher hands them
+// out in that order.
 // =============================================================================================
 constexpr uint32_t LANE_SIZES = LZ2_WAVE;                  // sizes 0..127 (8..127 occur)
 
@@ -1207,7 +1113,7 @@ void k_lz2_lane_place(LzP P, Lz2Scratch sc)
 }
 
 // Wave g of the launch replays clusters of one size n in [size_lo, size_hi], the waves of size 127 first.  budget_dw = dynamic
-// LDS of the launch in dwords (>= lz2_lane_region(127)).  The step body is that of k_lz2_mid_direct.
+// LDS of the launch in dwords (>= lz2_lane_region(127)).
 __global__ __launch_bounds__(64)
 void k_lz2_lanes(LzP P, Lz2Scratch sc, uint32_t size_hi, uint32_t size_lo, uint32_t budget_dw)
 {
@@ -1238,6 +1144,9 @@ void k_lz2_lanes(LzP P, Lz2Scratch sc, uint32_t size_hi, uint32_t size_lo, uint3
     if (lane < nl && dv.z != n) lz_order_violation(P);
     const uint32_t cnt = (lane < nl && dv.z == n) ? n : 0u, W = 1u << P.wbits;
     const uint32_t anom = (dv.w & 0xFFFFu) == 0xFFFFu ? ~0u : (dv.w & 0xFFFFu), limit = (dv.w >> 16) == 0xFFFFu ? ~0u : (dv.w >> 16);
+    // Every lane walks its own cluster, so nothing coalesces, and 2-byte loads cost a cache line each: rocprofv3 showed
+    // 1.5 GB of HBM traffic per launch against 60 MB of entries (the lines do not survive in L1 between steps).  Clusters
+    // start on 16-byte boundaries (lz2.h), so a lane fetches EIGHT entries per load and stores eight results at once.
     const uint4 *vp = reinterpret_cast<const uint4 *>(sc.bigpos + (size_t)dv.x * LZ2_BIG_STRIDE + dv.y);
     const uint4 *vr = reinterpret_cast<const uint4 *>(sc.bigrs + (size_t)dv.x * LZ2_BIG_STRIDE + dv.y);
     const uint4 *vi = reinterpret_cast<const uint4 *>(sc.bigpid + (size_t)dv.x * LZ2_BIG_STRIDE + dv.y);
@@ -1315,10 +1224,6 @@ void k_lz2_scatter(Lz2Scratch sc, uint16_t *__restrict__ cand_by_pos /* [nb][655
     for (uint32_t j = threadIdx.x; j < nb; j += 1024) { const uint32_t p = bp[j], c = bc[j]; if (c != p) out[p] = (uint16_t)c; }    // c == p: a pad
 }
 
-template __global__ void k_lz2_mid_direct<16, 64>(LzP, Lz2Scratch, int);
-template __global__ void k_lz2_mid_direct<32, 64>(LzP, Lz2Scratch, int);
-template __global__ void k_lz2_mid_direct<64, 64>(LzP, Lz2Scratch, int);
-template __global__ void k_lz2_mid_direct<128, 48>(LzP, Lz2Scratch, int);
 template __global__ void k_lz2_big<LZ2_BIG_SMALL, 1>(LzP, Lz2Scratch, int);
 template __global__ void k_lz2_big<512, 1>(LzP, Lz2Scratch, int);
 template __global__ void k_lz2_big<256, 1>(LzP, Lz2Scratch, int);
@@ -1446,23 +1351,18 @@ mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, ui
 }
 
 // stage B: replay of the exported clusters (almost no LDS: runs beside the next batch's stage A)
-// which: 1 = the lane replays of 8..31-entry clusters, 4 = of 32..127-entry clusters (with k_lz2_lanes: all of them), 2 = the wave / row replays; 7 = all on `s`
+// which: 4 = the lane replays (8..127-entry clusters), 2 = the wave / row replays; 7 = both on `s`
 mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which)
 {
-    // Replay grids cover the worst case and the kernels stride, so any grid is correct.  MI_LZ_REPLAY_WAVES=k caps them at
-    // k workgroups per CU (0 / unset = worst case).  Measured (round 2, same box): persistent grids sized by LDS (16 / 12 /
-    // 7 / 5 / 16 waves per CU) left the lane classes unchanged and made the wave replay 10.9 -> 15.8 ms per GB — a static
-    // stride deals a wave whatever chain lengths it draws, the hardware dispatcher hands the next cluster to the first
-    // wave that is free.
+    // Replay grids cover the worst case and the kernels stride, so any grid is correct.  Measured (round 2, same box):
+    // persistent grids sized by LDS (16 / 12 / 7 / 5 / 16 waves per CU) left the lane classes unchanged and made the wave
+    // replay 10.9 -> 15.8 ms per GB — a static stride deals a wave whatever chain lengths it draws, the hardware dispatcher
+    // hands the next cluster to the first wave that is free.
     const uint32_t ncu = (uint32_t)ctx->num_cu;
-    auto grid_of = [&](uint64_t worst) -> uint32_t {
-        const uint64_t g = (uint64_t)ncu * lz2_env_u32("MI_LZ_REPLAY_WAVES", 0);             // 0 = the worst-case grid
-        return (uint32_t)((g == 0 || worst < g) ? (worst ? worst : 1) : g);
-    };
-    // the lane classes: ordering pass + ONE launch of k_lz2_lanes (one-batch calls: on the stream of `which & 4`); MI_LZ_LANES=0:
-    // the four per-class launches of k_lz2_mid_direct (A/B).  MI_LZ_LANES_KIB: LDS per wave of k_lz2_lanes (A/B).
-    static const bool lanes = !(getenv("MI_LZ_LANES") && getenv("MI_LZ_LANES")[0] == '0');
-    if (lanes && (which & 4)) {
+    auto grid_of = [](uint64_t worst) -> uint32_t { return (uint32_t)(worst ? worst : 1); };
+    // the lane classes: ordering pass + ONE launch of k_lz2_lanes (one-batch calls: on the stream of `which & 4`).
+    // MI_LZ_LANES_KIB: LDS per wave of k_lz2_lanes (A/B).
+    if (which & 4) {
         static const uint32_t kib_env = lz2_env_u32("MI_LZ_LANES_KIB", 8);
         const uint32_t kib = kib_env < 1u ? 1u : kib_env > 32u ? 32u : kib_env, budget_dw = kib * 256u;    // >= lz2_lane_region(127)
         const uint64_t worst = (uint64_t)nb * lz2_class_cap(7);                  // lane-class clusters of the batch, at most
@@ -1476,19 +1376,6 @@ mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &
         const uint64_t waves = (uint64_t)nb * LZ_MAX_BLOCK / m + LANE_SIZES;
         { mi_prof_scope p(ctx, "k_lz2_lanes", s, (uint64_t)nb * P.block);
           hipLaunchKernelGGL(k_lz2_lanes, dim3((uint32_t)waves), dim3(64), budget_dw * 4u, s, P, sc, LANE_SIZES - 1u, LZ2_BIG, budget_dw); }
-    }
-    if (!lanes && (which & 1)) {
-    { mi_prof_scope p(ctx, "k_lz2_mid<16>", s, (uint64_t)nb * P.block);
-      hipLaunchKernelGGL((k_lz2_mid_direct<16, 64>), dim3(grid_of((uint64_t)nb * lz2_class_cap(7) / 64 + 1)), dim3(64), 0, s, P, sc, 7); }
-    { mi_prof_scope p(ctx, "k_lz2_mid<32>", s, (uint64_t)nb * P.block);
-      hipLaunchKernelGGL((k_lz2_mid_direct<32, 64>), dim3(grid_of((uint64_t)nb * lz2_class_cap(0) / 64 + 1)), dim3(64), 0, s, P, sc, 0); }
-    }
-    if (!lanes && (which & 4)) {
-    { mi_prof_scope p(ctx, "k_lz2_mid<64>", s, (uint64_t)nb * P.block);
-      hipLaunchKernelGGL((k_lz2_mid_direct<64, 64>), dim3(grid_of((uint64_t)nb * lz2_class_cap(1) / 64 + 1)), dim3(64), 0, s, P, sc, 1); }
-    { mi_prof_scope p(ctx, "k_lz2_mid<128>", s, (uint64_t)nb * P.block);
-      // 48 clusters per wave: 31 KiB of LDS instead of 42, five waves per CU instead of three (240 replaying lanes, not 192)
-      hipLaunchKernelGGL((k_lz2_mid_direct<128, 48>), dim3(grid_of((uint64_t)nb * lz2_class_cap(2) / 48 + 1)), dim3(64), 0, s, P, sc, 2); }
     }
     if (which & 2) {
     { mi_prof_scope p(ctx, "k_lz2_big", s, (uint64_t)nb * P.block);

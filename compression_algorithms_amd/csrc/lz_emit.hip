@@ -523,140 +523,66 @@ __device__ __forceinline__ uint32_t stream_bits(const uint8_t *s, uint64_t nbyte
 // =============================================================================================
 // host side
 // =============================================================================================
-// mode_h = 0: the reference's token stream, packed per block into the block's slot, placed by the scan / concatenate
-// kernels.  mode_h = 1: the same tokens, entropy coded per block (defh.hip); a record's size follows from its tally and code
-// lengths and records are whole dwords, so the scan runs BEFORE the pack and the pack writes every record where it belongs:
-// no slot, no k_lz_concat, the compressed bytes cross HBM once.  mode_h = 2 (z != nullptr): the same tokens as standard
-// DEFLATE records (defz.hip), byte aligned, through slot / scan / concatenate behind the container header; the caller has
-// checked the parameters and the capacity.  z->batch (deflate_batch.hip): mode Z over a batch of independent items — the blocks
-// come from a descriptor table built on the device (d_in, n, d_out, cap_bytes and d_block_bits are not used; nblocks is the
-// caller's bound), and stage C places every record in its own item's buffer instead of scan / concatenate.
-mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
-                         uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, int mode_h,
-                         const DefzCall *z)
+// The forms of one pipeline (LzForm, internal.h).  LZ_TOKENS: the reference's token stream, packed per block into the block's
+// slot, placed by the scan / concatenate kernels.  LZ_H: the same tokens, entropy coded per block (defh.hip); a record's size
+// follows from its tally and code lengths and records are whole dwords, so the scan runs BEFORE the pack and the pack writes
+// every record where it belongs: no slot, no k_lz_concat, the compressed bytes cross HBM once.  LZ_Z: the same tokens as
+// standard DEFLATE records (defz.hip), byte aligned, through slot / scan / concatenate behind the container header; the caller
+// has checked the parameters and the capacity.  LZ_BGZF: mode Z's records, each framed as a gzip member in its slot first
+// (bgzf.hip).  LZ_BATCH (deflate_batch.hip): mode Z over a batch of independent items — the blocks come from a descriptor table
+// built on the device (d_in, n, d_out, cap_bytes and d_block_bits are not used; nblocks is the caller's bound), and stage C
+// places every record in its own item's buffer instead of scan / concatenate.
+
+// blocks above 64 KiB (lz77 flavour): the HBM-resident finder of lzw.hip, one stream, batches sized by workspace
+static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
+                                uint64_t *d_block_bits, uint64_t nblocks, hipStream_t s)
 {
-    const DfbCall *const dfb = z ? z->batch : nullptr;      // a batch of independent items
-    if (!ctx || (!dfb && (!d_out || !d_block_bits || (n && !d_in)))) return MI_ERR_ARG;
-    mi_status st = lz_check_params(p);
+    mi_status st;
+    uint32_t nbw = lzw_batch_blocks(ctx, nblocks, P.block);
+    // (a workspace the context already holds is reused whatever its size; a batch that does not fit is halved)
+    while ((st = mi_ws_reserve(ctx, lzw_scratch_bytes(nbw, P.block) + 4096)) == MI_ERR_NOMEM && nbw > 1) nbw = (nbw + 1) / 2;
     if (st) return st;
-    if (!dfb && ((uintptr_t)d_out & 3u) != 0) return MI_ERR_ARG;
-    if (mode_h == 1 && (!p->deflate || p->lbits > 5 || p->wbits > 16)) return MI_ERR_ARG;
-    if (mode_h != 2 && cap_bytes < (mode_h ? mi_deflate_h_bound_bytes(n, p) : mi_lz_bound_bytes(n, p))) return MI_ERR_CAPACITY;
-    hipStream_t s = (hipStream_t)stream;
-    LzP P = lz_params_of(ctx, p);
-    if (dfb) P.flags |= LZP_DESC;
-    const uint64_t nblocks = dfb ? dfb->max_blocks : (n + P.block - 1) / P.block;
-    if (P.block > LZ_MAX_BLOCK) {
-        // blocks above 64 KiB (lz77 flavour): the HBM-resident finder of lzw.hip, one stream, batches sized by workspace
-        if (mode_h) return MI_ERR_ARG;
-        uint32_t nbw = lzw_batch_blocks(ctx, nblocks, P.block);
-        // (a workspace the context already holds is reused whatever its size; a batch that does not fit is halved)
-        while ((st = mi_ws_reserve(ctx, lzw_scratch_bytes(nbw, P.block) + 4096)) == MI_ERR_NOMEM && nbw > 1) nbw = (nbw + 1) / 2;
-        if (st) return st;
-        LzwScratch ws;
-        lzw_carve(ctx, nbw, P.block, &ws);
-        uint64_t *base_bits_w = reinterpret_cast<uint64_t *>((uint8_t *)ctx->ws + lzw_scratch_bytes(nbw, P.block));
-        MI_HIP(ctx, hipMemsetAsync(base_bits_w, 0, 8, s));
-        if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return MI_OK; }
-        for (uint64_t b0 = 0; b0 < nblocks; b0 += nbw) {
-            const uint32_t nb = (uint32_t)((nblocks - b0) < nbw ? (nblocks - b0) : nbw);
-            st = lzw_or_lzs_find(ctx, P, d_in, n, b0, nb, ws, s);
-            if (st) return st;
-            { mi_prof_scope pr(ctx, "k_lzw_parse_emit", s, (uint64_t)nb * P.block);
-              lzw_launch_parse_emit(d_in, n, P, ws, b0, nb, s); }
-            hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, s, ws.block_bits, nb, base_bits_w, ws.block_bits, d_block_bits + b0);
-            { mi_prof_scope pr(ctx, "k_lz_concat", s, (uint64_t)nb * P.block);
-              const uint64_t typw = (uint64_t)nb * (P.block / 4 + 64);
-              hipLaunchKernelGGL(k_lz_concat, dim3((unsigned)((typw + 255) / 256 < 65535 ? (typw + 255) / 256 : 65535)), dim3(256), 0, s, ws.slot, ws.block_bits, nb,
-                                 base_bits_w, reinterpret_cast<uint32_t *>(d_out), cap_bytes / 4, ws.slot_words); }
-            hipLaunchKernelGGL(k_lz_advance, dim3(1), dim3(1), 0, s, base_bits_w, ws.block_bits, nb);
-        }
-        MI_HIP(ctx, hipGetLastError());
-        return MI_OK;
-    }
-    const uint32_t nbmax = lz_batch_blocks(ctx, nblocks);
-    // three stages on three streams, MI_SETS scratch sets in rotation:
-    //   `s`          partition + find of batch i+2          (LDS heavy: one / three workgroups per CU)
-    //   ctx->side    replay of the exported clusters of i+1 (almost no LDS: runs beside the find)
-    //   ctx->parse   parse / emit / concatenate of batch i  (one 150 KiB workgroup per CU; the stream has raised priority)
-    // plus ctx->fb for the normally empty fallback chain.  Fork/join with events only: no host synchronisation.
-    const bool overlap = nblocks > nbmax && !getenv("MI_LZ_NO_OVERLAP");
-    const int nsets = overlap ? MI_SETS : 1;
-    const size_t set_bytes = mi_align_up(lz_scratch_bytes(nbmax), 4096);
-    const size_t trec_bytes = mode_h ? (size_t)nbmax * LZ_MAX_BLOCK * 4 : 0;       // token records, one array per set
-    const size_t z_bytes = dfb ? dfb_ws_bytes(*dfb) : z ? defz_ws_bytes() : 0;  // mode Z: the checksum's partials; a batch: its tables
-    st = mi_ws_reserve(ctx, set_bytes * nsets + 8192 + trec_bytes * nsets + z_bytes);
-    if (st) return st;
-    LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS];
-    for (int k = 0; k < nsets; ++k) lz_carve(ctx, nbmax, &sc[k], &sc2[k], k);
-    uint64_t *base_bits = reinterpret_cast<uint64_t *>((uint8_t *)ctx->ws + set_bytes * nsets);
-    uint32_t *trec_base = reinterpret_cast<uint32_t *>((uint8_t *)ctx->ws + set_bytes * nsets + 8192);
-    void *zws = (uint8_t *)ctx->ws + set_bytes * nsets + 8192 + trec_bytes * nsets;
-    if (dfb) {
-        st = dfb_begin(ctx, *dfb, P.block, zws, s, &d_in);                         // (d_in: the descriptor table from here on)
-        if (st) return st;
-        if (nblocks == 0) return dfb_end(ctx, *dfb, P.block, zws, s);
-    } else if (z) {
-        st = defz_begin(ctx, z->container, d_in, n, d_out, base_bits, zws, s);       // (the base starts at the header's bits)
-        if (st) return st;
-        if (nblocks == 0 && z->bgzf) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return bgzf_end(ctx, d_out, d_block_bits, 0, z->d_out_bytes, s); }
-        if (nblocks == 0) return defz_end(ctx, z->container, d_out, d_block_bits, 0, n, zws, z->d_out_bytes, s);
-    } else MI_HIP(ctx, hipMemsetAsync(base_bits, 0, 8, s));
+    LzwScratch ws;
+    lzw_carve(ctx, nbw, P.block, &ws);
+    uint64_t *base_bits_w = reinterpret_cast<uint64_t *>((uint8_t *)ctx->ws + lzw_scratch_bytes(nbw, P.block));
+    MI_HIP(ctx, hipMemsetAsync(base_bits_w, 0, 8, s));
     if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return MI_OK; }
-    hipStream_t sb = overlap ? ctx->side : s, sp = overlap ? ctx->parse : s;
-    // stage C of one batch (set k): parse / emit, then scan / concatenate (mode T; mode Z behind its entropy stage) or
-    // mode H's entropy stage with the scan inside it, then the base moves on
-    uint64_t placed = 0;                                           // batches handed to dfb_launch_place so far
-    auto stage_c = [&](int k, uint64_t b0, uint32_t nb) -> mi_status {
-        uint64_t *excl_local = sc[k].block_bits;                   // reused in place by the scan
-        uint32_t *trec = mode_h ? trec_base + (size_t)k * nbmax * LZ_MAX_BLOCK : nullptr;
-        {
-            mi_prof_scope pr(ctx, "k_lz_parse_emit", sp, (uint64_t)nb * P.block);
-            if (dfb) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
-            else hipLaunchKernelGGL(k_lz_parse_emit<false>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
-        }
-        if (mode_h == 1) {
-            mi_prof_scope ph(ctx, "k_defh_encode", sp, (uint64_t)nb * P.block);
-            defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, base_bits, d_block_bits + b0, d_out, cap_bytes, sp);
-        } else if (mode_h == 2) {
-            {
-                mi_prof_scope ph(ctx, "k_defz_encode", sp, (uint64_t)nb * P.block);
-                defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, dfb != nullptr, sp);
-            }
-            if (dfb) {
-                // every record to its own item (batches reach this stream in order: the item that straddles two of them goes on
-                // where the one before stopped)
-                mi_prof_scope pl(ctx, "k_dfb_place", sp, (uint64_t)nb * P.block);
-                dfb_launch_place(*dfb, zws, sc[k].slot, sc[k].block_bits, b0, nb, placed++, sp);
-                if (overlap) MI_HIP(ctx, hipEventRecord(ctx->ev_done[k], sp));
-                return MI_OK;
-            }
-            if (z->bgzf) {
-                mi_prof_scope pf(ctx, "k_bgzf_frame", sp, (uint64_t)nb * P.block);
-                bgzf_launch_frame(sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp);
-            }
-        }
-        if (mode_h != 1) {
-            hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, sp, sc[k].block_bits, nb, base_bits, excl_local, d_block_bits + b0);
-            mi_prof_scope pr(ctx, "k_lz_concat", sp, (uint64_t)nb * P.block);
-            const uint64_t typw = (uint64_t)nb * (P.block / 4 + 64);   // about one output byte per input byte; the kernel strides
-            hipLaunchKernelGGL(k_lz_concat, dim3((unsigned)((typw + 255) / 256)), dim3(256), 0, sp, sc[k].slot, excl_local, nb,
-                               base_bits, reinterpret_cast<uint32_t *>(d_out), cap_bytes / 4, (uint32_t)LZ_SLOT_WORDS);
-        }
-        hipLaunchKernelGGL(k_lz_advance, dim3(1), dim3(1), 0, sp, base_bits, excl_local, nb);
-        if (overlap) MI_HIP(ctx, hipEventRecord(ctx->ev_done[k], sp));
-        return MI_OK;
-    };
-    // MI_LZ_SCHED=1 holds the parse of batch i-1 until the partition of batch i is through (both want a whole CU's LDS for
-    // one workgroup and the partition is on the chain the pipeline waits for).  Measured: no difference (12.66 vs 12.65
-    // GB/s, partition 22.2 vs 22.6 ms) — the pipeline is bound by the total work, not by one chain.  Left as a switch.
-    const bool hold_parse = overlap && lz_use_v2() && getenv("MI_LZ_SCHED") != nullptr;
-#ifdef MI_MEASURE
-    // measurement builds only (make EXTRA=-DMI_MEASURE): what would the step cost if a stage were free?  The stream is WRONG.
-    const int skip = getenv("MI_LZ_SKIP") ? atoi(getenv("MI_LZ_SKIP")) : 0;       // 1: no stage B, 2: no stage C, 3: neither
-#else
-    const int skip = 0;
-#endif
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += nbw) {
+        const uint32_t nb = (uint32_t)((nblocks - b0) < nbw ? (nblocks - b0) : nbw);
+        st = lzw_or_lzs_find(ctx, P, d_in, n, b0, nb, ws, s);
+        if (st) return st;
+        { mi_prof_scope pr(ctx, "k_lzw_parse_emit", s, (uint64_t)nb * P.block);
+          lzw_launch_parse_emit(d_in, n, P, ws, b0, nb, s); }
+        hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, s, ws.block_bits, nb, base_bits_w, ws.block_bits, d_block_bits + b0);
+        { mi_prof_scope pr(ctx, "k_lz_concat", s, (uint64_t)nb * P.block);
+          const uint64_t typw = (uint64_t)nb * (P.block / 4 + 64);
+          hipLaunchKernelGGL(k_lz_concat, dim3((unsigned)((typw + 255) / 256 < 65535 ? (typw + 255) / 256 : 65535)), dim3(256), 0, s, ws.slot, ws.block_bits, nb,
+                             base_bits_w, reinterpret_cast<uint32_t *>(d_out), cap_bytes / 4, ws.slot_words); }
+        hipLaunchKernelGGL(k_lz_advance, dim3(1), dim3(1), 0, s, base_bits_w, ws.block_bits, nb);
+    }
+    MI_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+
+// the workspace behind the scratch sets (lz_carve): the output's running bit position, the token records of every form but
+// LZ_TOKENS (one array per set), and what the form keeps for itself (mode Z: the checksum's partials; a batch: its tables)
+struct LzTail { uint64_t *base_bits; uint32_t *trec; void *zws; size_t bytes; };                // bytes: sets and tail together
+
+static LzTail lz_carve_tail(void *ws, size_t sets_bytes, size_t trec_words, size_t z_bytes)
+{
+    mi_carver cv((uint8_t *)ws + sets_bytes);
+    LzTail t;
+    t.base_bits = reinterpret_cast<uint64_t *>(cv.take<uint8_t>(8192));
+    t.trec = trec_words ? cv.take<uint32_t>(trec_words) : nullptr;
+    t.zws = cv.take<uint8_t>(z_bytes);
+    t.bytes = sets_bytes + cv.off;
+    return t;
+}
+
+// The stream of the fallback chains of the ODD batches of a pipelined call (the even ones' is ctx->fb); creates or releases
+// ctx->fb2.  `sb`: stage B's stream.
+static hipStream_t lz_odd_fallback_stream(mi_ctx *ctx, bool overlap, hipStream_t sb)
+{
     // The fallback chains of consecutive batches go to two streams WHEN the input lives in the fallback: their kernels are long
     // serial chains on few workgroups and overlap well — pages 1.72 -> 2.16, runs 1.65 -> 2.77 GB/s on 10^8 B.  On text a second
     // stream costs 7 % even idle (20.4 -> 19.1 GB/s, whatever GPU_MAX_HW_QUEUES says), so it exists only while the hint says so.
@@ -684,88 +610,170 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         if (hipStreamQuery(ctx->fb2) == hipSuccess) { (void)hipStreamDestroy(ctx->fb2); ctx->fb2 = nullptr; }
         else (void)hipGetLastError();                     // still draining an earlier call's chains: try again next time
     }
-    uint64_t batch = 0, prev_b0 = 0; uint32_t prev_nb = 0; int prev_k = -1;
-    // MI_LZ_TAPER=1: the last batches taper (full batches while two or more are left, then halves down to a quarter batch).  When
-    // the last find has finished only that batch's replay and parse are left, one small kernel after the other on an emptying GPU:
-    // ~6 ms of a 47.8 ms step with five equal batches (kernel timeline, round 4).  Measured: 21.17 -> 20.89 GB/s — the shorter
-    // drain is worth less than what seven batches instead of five cost; off by default.
-    static const bool taper = getenv("MI_LZ_TAPER") && getenv("MI_LZ_TAPER")[0] == '1';
-    uint32_t nb_next = 0;
-    for (uint64_t b0 = 0; b0 < nblocks; b0 += nb_next, ++batch) {
-        const uint64_t rem = nblocks - b0;
-        uint32_t nb = (uint32_t)(rem < nbmax ? rem : nbmax);
-        if (taper && overlap && rem < 2ull * nbmax && rem > nbmax / 4u) {
-            const uint64_t half = (rem + 1) / 2;
-            nb = (uint32_t)(half > nbmax / 4u ? half : nbmax / 4u);
-            if (nb > nbmax) nb = nbmax;
+    return fb2_side ? sb : (fb_busy && ctx->fb2) ? ctx->fb2 : ctx->fb;
+}
+
+// Stage B of a call of ONE batch (no pipeline: the side and fallback streams are idle): the lane replays run BESIDE the wave / row
+// replays, on the side stream — the two groups are independent, each is a chain of launches with tails, and what follows needs
+// both; the (normally empty) fallback chain and the wide finder have left the partition -> find chain for the fallback stream as
+// in the pipeline (MI_LZ_B_SPLIT=0: one chain on one stream, A/B)
+static mi_status lz_stage_b_solo(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s)
+{
+    MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_wide[0], 0));                                             // the wide parts' exports
+    MI_HIP(ctx, hipEventRecord(ctx->ev_find[0], s));
+    MI_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_find[0], 0));
+    mi_status st = lz_find_stage_b(ctx, P, nb, sc2, ctx->side, 4);
+    if (st) return st;
+    MI_HIP(ctx, hipEventRecord(ctx->ev_replay[0], ctx->side));
+    st = lz_find_stage_b(ctx, P, nb, sc2, s, 2);
+    MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_replay[0], 0));
+    MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_fb[0], 0));                                               // the fallback blocks' candidates
+    return st;
+}
+
+mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
+                         uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, const LzCall &c)
+{
+    const bool items = c.form == LZ_BATCH;                         // a batch of independent items brings its own buffers
+    if (!ctx || (!items && (!d_out || !d_block_bits || (n && !d_in)))) return MI_ERR_ARG;
+    mi_status st = lz_check_params(p);
+    if (st) return st;
+    if (!items && ((uintptr_t)d_out & 3u) != 0) return MI_ERR_ARG;
+    if (c.form == LZ_H && (!p->deflate || p->lbits > 5 || p->wbits > 16)) return MI_ERR_ARG;
+    if (c.form == LZ_TOKENS && cap_bytes < mi_lz_bound_bytes(n, p)) return MI_ERR_CAPACITY;
+    if (c.form == LZ_H && cap_bytes < mi_deflate_h_bound_bytes(n, p)) return MI_ERR_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    LzP P = lz_params_of(ctx, p);
+    if (items) P.flags |= LZP_DESC;
+    const uint64_t nblocks = items ? c.batch->max_blocks : (n + P.block - 1) / P.block;
+    if (P.block > LZ_MAX_BLOCK)
+        return c.form == LZ_TOKENS ? lz_encode_wide(ctx, P, d_in, n, d_out, cap_bytes, d_block_bits, nblocks, s) : MI_ERR_ARG;
+    const uint32_t nbmax = lz_batch_blocks(ctx, nblocks);
+    // three stages on three streams, MI_SETS scratch sets in rotation:
+    //   `s`          partition + find of batch i+2          (LDS heavy: one / three workgroups per CU)
+    //   ctx->side    replay of the exported clusters of i+1 (almost no LDS: runs beside the find)
+    //   ctx->parse   parse / emit / concatenate of batch i  (one 150 KiB workgroup per CU; the stream has raised priority)
+    // plus ctx->fb for the normally empty fallback chain.  Fork/join with events only: no host synchronisation.
+    const bool overlap = nblocks > nbmax && !getenv("MI_LZ_NO_OVERLAP");
+    const int nsets = overlap ? MI_SETS : 1;
+    const size_t sets_bytes = mi_align_up(lz_scratch_bytes(nbmax), 4096) * nsets;
+    const size_t trec_words = c.form == LZ_TOKENS ? 0 : (size_t)nbmax * LZ_MAX_BLOCK * nsets;
+    const size_t z_bytes = items ? dfb_ws_bytes(*c.batch) : (c.form == LZ_Z || c.form == LZ_BGZF) ? defz_ws_bytes() : 0;
+    st = mi_ws_reserve(ctx, lz_carve_tail(nullptr, sets_bytes, trec_words, z_bytes).bytes);
+    if (st) return st;
+    LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS];
+    for (int k = 0; k < nsets; ++k) lz_carve(ctx, nbmax, &sc[k], &sc2[k], k);
+    const LzTail t = lz_carve_tail(ctx->ws, sets_bytes, trec_words, z_bytes);
+    // in front of the first block: where the output's bits start, and what the form needs before its blocks
+    switch (c.form) {
+    case LZ_TOKENS: case LZ_H: MI_HIP(ctx, hipMemsetAsync(t.base_bits, 0, 8, s)); break;
+    case LZ_Z: case LZ_BGZF:   st = defz_begin(ctx, c.container, d_in, n, d_out, t.base_bits, t.zws, s); break;   // (the base starts at the header's bits)
+    case LZ_BATCH:             st = dfb_begin(ctx, *c.batch, P.block, t.zws, s, &d_in); break;                    // (d_in: the descriptor table from here on)
+    }
+    if (st) return st;
+    // behind the last block.  The table of an empty input is its one closing entry (mode Z's epilogue writes it itself, a batch
+    // has no table).
+    auto finish = [&]() -> mi_status {
+        if (nblocks == 0 && (c.form == LZ_TOKENS || c.form == LZ_H || c.form == LZ_BGZF)) MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s));
+        switch (c.form) {
+        case LZ_TOKENS: case LZ_H: return MI_OK;
+        case LZ_Z:                 return defz_end(ctx, c.container, d_out, d_block_bits, nblocks, n, t.zws, c.d_out_bytes, s);
+        case LZ_BGZF:              return bgzf_end(ctx, d_out, d_block_bits, nblocks, c.d_out_bytes, s);
+        case LZ_BATCH:             return dfb_end(ctx, *c.batch, P.block, t.zws, s);
         }
-        nb_next = nb;
+        return MI_ERR_ARG;
+    };
+    if (nblocks == 0) return finish();
+    hipStream_t sb = overlap ? ctx->side : s, sp = overlap ? ctx->parse : s;
+    // stage C of one batch (set k, the seq-th of the call): parse / emit, what the form does with the tokens, then the base moves on
+    auto stage_c = [&](int k, uint64_t b0, uint32_t nb, uint64_t seq) {
+        const uint64_t pbytes = (uint64_t)nb * P.block;
+        uint64_t *excl_local = sc[k].block_bits;                   // reused in place by the scan
+        uint32_t *trec = t.trec ? t.trec + (size_t)k * nbmax * LZ_MAX_BLOCK : nullptr;
+        {
+            mi_prof_scope pr(ctx, "k_lz_parse_emit", sp, pbytes);
+            if (items) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
+            else hipLaunchKernelGGL(k_lz_parse_emit<false>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
+        }
+        auto defh = [&] { mi_prof_scope ph(ctx, "k_defh_encode", sp, pbytes);     // mode H's entropy stage, the scan inside it: straight into the stream
+                          defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, t.base_bits, d_block_bits + b0, d_out, cap_bytes, sp); };
+        auto defz = [&] { mi_prof_scope ph(ctx, "k_defz_encode", sp, pbytes);     // mode Z's entropy stage: records in their slots
+                          defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, items, sp); };
+        auto frame = [&] { mi_prof_scope pf(ctx, "k_bgzf_frame", sp, pbytes);     // every record a gzip member
+                           bgzf_launch_frame(sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp); };
+        // every record to its own item (batches reach this stream in order: the item that straddles two of them goes on where the
+        // one before stopped)
+        auto place = [&] { mi_prof_scope pl(ctx, "k_dfb_place", sp, pbytes);
+                           dfb_launch_place(*c.batch, t.zws, sc[k].slot, sc[k].block_bits, b0, nb, seq, sp); };
+        auto concat = [&] {                                        // the slots' contents into the one output stream: scan, then concatenate
+            hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, sp, sc[k].block_bits, nb, t.base_bits, excl_local, d_block_bits + b0);
+            mi_prof_scope pr(ctx, "k_lz_concat", sp, pbytes);
+            const uint64_t typw = (uint64_t)nb * (P.block / 4 + 64);   // about one output byte per input byte; the kernel strides
+            hipLaunchKernelGGL(k_lz_concat, dim3((unsigned)((typw + 255) / 256)), dim3(256), 0, sp, sc[k].slot, excl_local, nb,
+                               t.base_bits, reinterpret_cast<uint32_t *>(d_out), cap_bytes / 4, (uint32_t)LZ_SLOT_WORDS);
+        };
+        auto advance = [&] { hipLaunchKernelGGL(k_lz_advance, dim3(1), dim3(1), 0, sp, t.base_bits, excl_local, nb); };
+        switch (c.form) {
+        case LZ_TOKENS: concat(); advance(); break;
+        case LZ_H:      defh(); advance(); break;
+        case LZ_Z:      defz(); concat(); advance(); break;
+        case LZ_BGZF:   defz(); frame(); concat(); advance(); break;
+        case LZ_BATCH:  defz(); place(); break;
+        }
+    };
+#ifdef MI_MEASURE
+    // measurement builds only (make EXTRA=-DMI_MEASURE): what would the step cost if a stage were free?  The stream is WRONG.
+    const int skip = getenv("MI_LZ_SKIP") ? atoi(getenv("MI_LZ_SKIP")) : 0;       // 1: no stage B, 2: no stage C, 3: neither
+#else
+    const int skip = 0;
+#endif
+    const hipStream_t sf_odd = lz_odd_fallback_stream(ctx, overlap, sb);
+    static const bool b_split = !(getenv("MI_LZ_B_SPLIT") && getenv("MI_LZ_B_SPLIT")[0] == '0');
+    const bool solo = !overlap && b_split && lz_use_v2() && !skip;
+    uint64_t batch = 0; uint32_t nb = 0;
+    for (uint64_t b0 = 0; b0 < nblocks; b0 += nb, ++batch) {
+        nb = (uint32_t)(nblocks - b0 < nbmax ? nblocks - b0 : nbmax);
         const int k = (int)(batch % (uint64_t)nsets);
         if (overlap && batch >= (uint64_t)nsets) MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_done[k], 0));   // set k is free again
-        static const bool b_split = !(getenv("MI_LZ_B_SPLIT") && getenv("MI_LZ_B_SPLIT")[0] == '0');
-        const bool solo = !overlap && b_split && lz_use_v2() && !skip;
-        st = lz_find_stage_a(ctx, P, d_in, n, b0, nb, sc[k], sc2[k], s,
-                             overlap ? ((batch & 1u) && fb_busy && (ctx->fb2 || fb2_side) ? (fb2_side ? sb : ctx->fb2) : ctx->fb) : (solo ? ctx->fb : s), ctx->ev_part[k], ctx->ev_fb[k], ctx->ev_wide[k]);
+        // stage A: partition + find on `s`, the fallback chain and the wide finder beside them
+        const hipStream_t sf = !overlap ? (solo ? ctx->fb : s) : (batch & 1u) ? sf_odd : ctx->fb;
+        st = lz_find_stage_a(ctx, P, d_in, n, b0, nb, sc[k], sc2[k], s, sf, ctx->ev_part[k], ctx->ev_fb[k], ctx->ev_wide[k]);
         if (st) return st;
-        if (hold_parse && prev_k >= 0) {
-            MI_HIP(ctx, hipStreamWaitEvent(sp, ctx->ev_part[k], 0));
-            st = stage_c(prev_k, prev_b0, prev_nb);
-            if (st) return st;
-        }
+        // stage B: the replays, behind the find and the wide parts' exports (lz_find.hip)
         if (overlap) {
             MI_HIP(ctx, hipEventRecord(ctx->ev_find[k], s)); MI_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_find[k], 0));
-            if (lz_use_v2() && !getenv("MI_LZ_WIDE_INLINE")) MI_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_wide[k], 0));    // the wide parts' exports (lz_find.hip)
+            if (lz_use_v2()) MI_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_wide[k], 0));
         }
-        // ONE batch (no pipeline: the side, parse and fallback streams are idle): the lane replays run BESIDE the wave / row replays, the
-        // long size classes on the side stream, the short ones on the parse stream — the groups are independent, each is a chain of
-        // launches with tails, and what follows needs all of them; the (normally empty) fallback chain and the wide finder leave the
-        // partition -> find chain for the fallback stream as in the pipeline (MI_LZ_B_SPLIT=0: one chain on one stream, A/B)
-        if (solo && !(skip & 1)) {
-            if (!getenv("MI_LZ_WIDE_INLINE")) MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_wide[0], 0));        // the wide parts' exports
-            MI_HIP(ctx, hipEventRecord(ctx->ev_find[0], s));
-            MI_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_find[0], 0)); MI_HIP(ctx, hipStreamWaitEvent(ctx->parse, ctx->ev_find[0], 0));
-            st = lz_find_stage_b(ctx, P, nb, sc2[k], ctx->side, 4);
-            if (st) return st;
-            MI_HIP(ctx, hipEventRecord(ctx->ev_replay[0], ctx->side));
-            st = lz_find_stage_b(ctx, P, nb, sc2[k], ctx->parse, 1);
-            if (st) return st;
-            MI_HIP(ctx, hipEventRecord(ctx->ev_done[0], ctx->parse));
-            st = lz_find_stage_b(ctx, P, nb, sc2[k], s, 2);
-            MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_replay[0], 0)); MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_done[0], 0));
-            MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_fb[0], 0));                                           // the fallback blocks' candidates
-        } else if (!(skip & 1)) st = lz_find_stage_b(ctx, P, nb, sc2[k], sb, 7);
+        if (solo) st = lz_stage_b_solo(ctx, P, nb, sc2[k], s);
+        else if (!(skip & 1)) st = lz_find_stage_b(ctx, P, nb, sc2[k], sb, 7);
         if (st) return st;
+        // join: stage C needs the replays' results and the fallback blocks' candidates
         if (overlap) {
             MI_HIP(ctx, hipEventRecord(ctx->ev_replay[k], sb));
             MI_HIP(ctx, hipStreamWaitEvent(sp, ctx->ev_replay[k], 0));
-            if (lz_use_v2()) MI_HIP(ctx, hipStreamWaitEvent(sp, ctx->ev_fb[k], 0));      // the fallback blocks' candidates
+            if (lz_use_v2()) MI_HIP(ctx, hipStreamWaitEvent(sp, ctx->ev_fb[k], 0));
         }
-        if (hold_parse) { prev_k = k; prev_b0 = b0; prev_nb = nb; }
-        else if (!(skip & 2)) { st = stage_c(k, b0, nb); if (st) return st; }
-        else if (overlap) MI_HIP(ctx, hipEventRecord(ctx->ev_done[k], sp));
+        if (!(skip & 2)) stage_c(k, b0, nb, batch);
+        if (overlap) MI_HIP(ctx, hipEventRecord(ctx->ev_done[k], sp));
     }
-    if (hold_parse && prev_k >= 0) { st = stage_c(prev_k, prev_b0, prev_nb); if (st) return st; }
     if (overlap) {                                                 // join: the last stage finishes everything
         MI_HIP(ctx, hipEventRecord(ctx->ev_fork, sp));
         MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_fork, 0));
     }
     MI_HIP(ctx, hipGetLastError());
-    if (dfb) return dfb_end(ctx, *dfb, P.block, zws, s);
-    if (z && z->bgzf) return bgzf_end(ctx, d_out, d_block_bits, nblocks, z->d_out_bytes, s);
-    if (z) return defz_end(ctx, z->container, d_out, d_block_bits, nblocks, n, zws, z->d_out_bytes, s);
-    return MI_OK;
+    return finish();
 }
 
 extern "C" mi_status mi_lz_encode_dev(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
                                       uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream)
 {
-    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, 0);
+    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, LzCall{LZ_TOKENS});
 }
 
 extern "C" mi_status mi_deflate_h_encode_dev(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
                                              uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream)
 {
-    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, 1);
+    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, LzCall{LZ_H});
 }
 
 extern "C" mi_status mi_deflate_z_encode_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, const uint8_t *d_in, uint64_t n,
@@ -775,8 +783,7 @@ extern "C" mi_status mi_deflate_z_encode_dev(mi_ctx *ctx, const mi_lz_params *p,
     mi_status st = defz_check(p, container);
     if (st) return st;
     if (cap_bytes < mi_deflate_z_bound_bytes(n, p, container)) return MI_ERR_CAPACITY;
-    const DefzCall z{container, d_out_bytes};
-    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, 2, &z);
+    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_block_bits, stream, LzCall{LZ_Z, container, d_out_bytes});
 }
 
 // BGZF (bgzf.hip has the framing): mode Z's records, each in a gzip member of its own
@@ -788,8 +795,7 @@ extern "C" mi_status mi_bgzf_encode_dev(mi_ctx *ctx, const mi_lz_params *p, cons
     if (st) return st;
     if (p->block > MI_BGZF_MAX_BLOCK) return MI_ERR_ARG;
     if (cap_bytes < mi_bgzf_bound_bytes(n, p)) return MI_ERR_CAPACITY;
-    const DefzCall z{MI_CONTAINER_RAW, d_out_bytes, true};
-    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_member_bits, stream, 2, &z);
+    return lz_encode_impl(ctx, p, d_in, n, d_out, cap_bytes, d_member_bits, stream, LzCall{LZ_BGZF, MI_CONTAINER_RAW, d_out_bytes});
 }
 
 // launch alone: errors accumulate in *err (an mi_err_slot the caller reads once everything it launched has run)

@@ -775,8 +775,6 @@ size_t lz_scratch_bytes(uint32_t nb)
     return per * nb + 16 * 256 + 4096 + lz2_scratch_bytes(nb) + 64 * 256;
 }
 
-mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                        const LzScratch &sc, hipStream_t s, const uint32_t *blist, const uint32_t *bcount);
 bool lz_use_v2()
 {
     const char *e = getenv("MI_LZ_V2");
@@ -800,65 +798,6 @@ void lz_carve(mi_ctx *ctx, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2, int set)
     if (sc2) lz2_carve(cv, nb, sc2);
 }
 
-// match finder for blocks [block0, block0+nb), in two stages so that a caller can overlap them across
-// batches: A = partition + find (+ the first pipeline for the blocks the LDS-resident path hands back, or
-// for everything when MI_LZ_V2=0); B = replay of the exported clusters.
-// `sf` = stream of the fallback chain (may equal `s`); when it differs the caller joins it before the parse:
-// the chain is normally empty, but its launches ask for 82..155 KiB of LDS per workgroup and would otherwise
-// sit in front of the real work waiting for that LDS.
-mi_status lz_find_stage_a(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                          const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s, hipStream_t sf, hipEvent_t ev_part, hipEvent_t ev_fb,
-                          hipEvent_t ev_wide)
-{
-    if (!lz_use_v2()) return lz_find_batch(ctx, P, d_in, n, block0, nb, sc, s, nullptr, nullptr);
-    mi_status st = lz2_stage_partition(ctx, P, d_in, n, block0, nb, sc2, s);
-    if (st) return st;
-    // MI_LZ_UNSAFE_NO_FALLBACK=1 (measurement only: wrong output for any block the partition hands back) leaves the
-    // fallback chain out, to price its normally empty launches
-    static const bool no_fb = getenv("MI_LZ_UNSAFE_NO_FALLBACK") != nullptr;
-    static const bool wide_inline = getenv("MI_LZ_WIDE_INLINE") != nullptr;      // A/B: the wide finder on the main stream as in round 3
-    if (sf != s) { MI_HIP(ctx, hipEventRecord(ev_part, s)); MI_HIP(ctx, hipStreamWaitEvent(sf, ev_part, 0)); }
-    const bool wide_aside = sf != s && ev_wide && !wide_inline;
-    if (wide_aside) {
-        // first thing on the side chain: stage B waits for it (exported clusters of wide parts), the fallback chain behind it does not matter
-        st = lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, sf, true);
-        if (st) return st;
-        MI_HIP(ctx, hipEventRecord(ev_wide, sf));
-    }
-    if (!no_fb) {
-        st = lz_find_batch(ctx, P, d_in, n, block0, nb, sc, sf, sc2.fallback_list, sc2.fallback_count);
-        if (st) return st;
-    }
-    if (sf != s) MI_HIP(ctx, hipEventRecord(ev_fb, sf));
-    st = lz2_stage_find(ctx, P, d_in, n, block0, nb, sc2, s);
-    if (st || wide_aside) return st;
-    return lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, s, false);
-}
-mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which)
-{
-    return lz_use_v2() ? lz2_stage_b(ctx, P, nb, sc2, s, which) : MI_OK;
-}
-mi_status lz_run_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                      const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s)
-{
-    mi_status st = lz_find_stage_a(ctx, P, d_in, n, block0, nb, sc, sc2, s, s, nullptr, nullptr, nullptr);
-    return st ? st : lz_find_stage_b(ctx, P, nb, sc2, s, 7);
-}
-mi_status lz_check_params(const mi_lz_params *p)
-{
-    if (!p) return MI_ERR_ARG;
-    if (p->wbits < 8 || p->wbits > 16) return MI_ERR_ARG;
-    if (p->lbits < 3 || p->lbits > 8) return MI_ERR_ARG;
-    if (p->tbits < 17 || p->tbits > 24) return MI_ERR_ARG;
-    // blocks above 64 KiB: the lz77 flavour only (lzw.hip), multiples of 256 bytes up to 1 MiB, so that WINDOW_BITS 16 slides
-    if (p->block < 1) return MI_ERR_ARG;
-    if (p->block > LZ_MAX_BLOCK && (p->deflate || p->block > (1u << 20) || (p->block & 255u) || p->lbits > 5)) return MI_ERR_ARG;
-    if (1u + p->wbits + p->lbits > 32) return MI_ERR_ARG;
-    return MI_OK;
-}
-
-mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                        const LzScratch &sc, hipStream_t s, const uint32_t *blist, const uint32_t *bcount);
 mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                         const LzScratch &sc, hipStream_t s, const uint32_t *blist, const uint32_t *bcount)
 {
@@ -906,6 +845,66 @@ mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t
     }
     ctx->profiling = saved_prof;
     MI_HIP(ctx, hipGetLastError());
+    return MI_OK;
+}
+
+// match finder for blocks [block0, block0+nb), in two stages so that a caller can overlap them across
+// batches: A = partition + find (+ the first pipeline for the blocks the LDS-resident path hands back, or
+// for everything when MI_LZ_V2=0); B = replay of the exported clusters.
+// `sf` = stream of the fallback chain (may equal `s`); when it differs the caller joins it before the parse:
+// the chain is normally empty, but its launches ask for 82..155 KiB of LDS per workgroup and would otherwise
+// sit in front of the real work waiting for that LDS.
+mi_status lz_find_stage_a(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
+                          const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s, hipStream_t sf, hipEvent_t ev_part, hipEvent_t ev_fb,
+                          hipEvent_t ev_wide)
+{
+    if (!lz_use_v2()) return lz_find_batch(ctx, P, d_in, n, block0, nb, sc, s, nullptr, nullptr);
+    mi_status st = lz2_stage_partition(ctx, P, d_in, n, block0, nb, sc2, s);
+    if (st) return st;
+#ifdef MI_MEASURE
+    // measurement builds only (make EXTRA=-DMI_MEASURE): MI_LZ_UNSAFE_NO_FALLBACK=1 leaves the fallback chain out, to price its
+    // normally empty launches.  The output is WRONG for any block the partition hands back.
+    static const bool no_fb = getenv("MI_LZ_UNSAFE_NO_FALLBACK") != nullptr;
+#else
+    const bool no_fb = false;
+#endif
+    if (sf != s) { MI_HIP(ctx, hipEventRecord(ev_part, s)); MI_HIP(ctx, hipStreamWaitEvent(sf, ev_part, 0)); }
+    const bool wide_aside = sf != s && ev_wide;
+    if (wide_aside) {
+        // first thing on the side chain: stage B waits for it (exported clusters of wide parts), the fallback chain behind it does not matter
+        st = lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, sf, true);
+        if (st) return st;
+        MI_HIP(ctx, hipEventRecord(ev_wide, sf));
+    }
+    if (!no_fb) {
+        st = lz_find_batch(ctx, P, d_in, n, block0, nb, sc, sf, sc2.fallback_list, sc2.fallback_count);
+        if (st) return st;
+    }
+    if (sf != s) MI_HIP(ctx, hipEventRecord(ev_fb, sf));
+    st = lz2_stage_find(ctx, P, d_in, n, block0, nb, sc2, s);
+    if (st || wide_aside) return st;
+    return lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, s, false);
+}
+mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which)
+{
+    return lz_use_v2() ? lz2_stage_b(ctx, P, nb, sc2, s, which) : MI_OK;
+}
+mi_status lz_run_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
+                      const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s)
+{
+    mi_status st = lz_find_stage_a(ctx, P, d_in, n, block0, nb, sc, sc2, s, s, nullptr, nullptr, nullptr);
+    return st ? st : lz_find_stage_b(ctx, P, nb, sc2, s, 7);
+}
+mi_status lz_check_params(const mi_lz_params *p)
+{
+    if (!p) return MI_ERR_ARG;
+    if (p->wbits < 8 || p->wbits > 16) return MI_ERR_ARG;
+    if (p->lbits < 3 || p->lbits > 8) return MI_ERR_ARG;
+    if (p->tbits < 17 || p->tbits > 24) return MI_ERR_ARG;
+    // blocks above 64 KiB: the lz77 flavour only (lzw.hip), multiples of 256 bytes up to 1 MiB, so that WINDOW_BITS 16 slides
+    if (p->block < 1) return MI_ERR_ARG;
+    if (p->block > LZ_MAX_BLOCK && (p->deflate || p->block > (1u << 20) || (p->block & 255u) || p->lbits > 5)) return MI_ERR_ARG;
+    if (1u + p->wbits + p->lbits > 32) return MI_ERR_ARG;
     return MI_OK;
 }
 

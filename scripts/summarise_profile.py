@@ -55,8 +55,6 @@ for b in ("bench_trace.json", "bench_fetch.json", "bench_write.json"):
 # per-kernel HBM bytes per launch under the names bench.py's own event timing uses (roofline.traffic reads this file)
 def bench_name(k):
     k = k.replace("void ", "").strip()
-    if k.startswith("k_lz2_mid_direct<"):
-        return "k_lz2_mid<" + k.split("<")[1].split(",")[0] + ">"
     if k.startswith("k_lz2_big<"):
         return "k_lz2_big" if k.split("<")[1].split(",")[0] in ("1024",) else "k_lz2_big<" + k.split("<")[1].split(",")[0] + ">"
     return k

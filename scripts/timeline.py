@@ -33,7 +33,7 @@ def union(iv):
         if s > ce: tot += ce - cs; cs, ce = s, e
         else: ce = max(ce, e)
     return tot + ce - cs
-groups = {"A": ("k_lz2_partition", "k_lz2_find"), "B": ("k_lz2_mid", "k_lz2_big"), "C": ("k_lz_parse", "k_defh", "k_lz_concat", "k_lz_scan"),
+groups = {"A": ("k_lz2_partition", "k_lz2_find"), "B": ("k_lz2_lane", "k_lz2_big"), "C": ("k_lz_parse", "k_defh", "k_lz_concat", "k_lz_scan"),
           "lzs": ("k_lzs", "void k_lzs", "k_lzw")}
 iv = [(s, e) for s, e, n in win]
 print("any kernel busy", round(union(iv) / 1e6, 3), "ms of", round((win[-1][1] - t0) / 1e6, 3))
