@@ -264,8 +264,6 @@ void k_bgzf_list(const uint8_t *__restrict__ s, uint64_t nbytes, BgzfChunks ck, 
     });
 }
 
-static size_t bgzf_index_ws(uint64_t nchunks) { return (size_t)(6u * 8u * nchunks + 6u * 256u); }
-
 extern "C" mi_status mi_bgzf_index_dev(mi_ctx *ctx, const uint8_t *d_stream, uint64_t stream_bytes, uint64_t *d_members,
                                        uint64_t cap_members, uint64_t *d_count, void *stream)
 {
@@ -274,12 +272,12 @@ extern "C" mi_status mi_bgzf_index_dev(mi_ctx *ctx, const uint8_t *d_stream, uin
     const uint64_t nchunks = (stream_bytes + BGZF_CHUNK - 1) / BGZF_CHUNK;
     if (nchunks > 0x7FFFFFFFull) return MI_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    mi_status st = mi_ws_reserve(ctx, bgzf_index_ws(nchunks));
-    if (st) return st;
-    mi_carver cv(ctx->ws);
     BgzfChunks ck;
-    ck.entry = cv.take<uint64_t>(nchunks); ck.exit_at = cv.take<uint64_t>(nchunks); ck.count = cv.take<uint64_t>(nchunks);
-    ck.isz = cv.take<uint64_t>(nchunks); ck.idx0 = cv.take<uint64_t>(nchunks); ck.out0 = cv.take<uint64_t>(nchunks);
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) {
+        cv.take(ck.entry, nchunks); cv.take(ck.exit_at, nchunks); cv.take(ck.count, nchunks);
+        cv.take(ck.isz, nchunks); cv.take(ck.idx0, nchunks); cv.take(ck.out0, nchunks);
+    });
+    if (st) return st;
     uint32_t *err = mi_err_slot(ctx, s);
     if (!err) return MI_ERR_HIP;
     {
@@ -351,9 +349,9 @@ extern "C" mi_status mi_bgzf_inflate_dev(mi_ctx *ctx, const uint8_t *d_stream, u
     if (n_members == 0) return out_bytes ? MI_ERR_ARG : MI_OK;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t nmem = (uint32_t)n_members;
-    mi_status st = mi_ws_reserve(ctx, (size_t)nmem * sizeof(InfSeg) + 256);
+    InfSeg *seg;
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(seg, nmem); });
     if (st) return st;
-    InfSeg *seg = (InfSeg *)ctx->ws;
     uint32_t *err = mi_err_slot(ctx, s);
     if (!err) return MI_ERR_HIP;
     hipLaunchKernelGGL(k_bgzf_segments, dim3((nmem + 255u) / 256u), dim3(256), 0, s, d_stream, stream_bytes, d_members, first_member,

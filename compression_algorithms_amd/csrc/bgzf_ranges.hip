@@ -68,7 +68,7 @@ static BgzrWs bgzr_carve(void *ws, const BgzrCall &c)
     w.seg_e = cv.take<InfSeg>(ne); w.st_e = cv.take<uint32_t>(ne);
     w.place = cv.take<BgzrPlace>(ne);
     w.cells = cv.take<uint8_t>((ne < BGZR_GROUP ? ne : (size_t)BGZR_GROUP) * BGZR_CELL);
-    w.bytes = mi_align_up(cv.off, 256);
+    w.bytes = cv.bytes();
     return w;
 }
 

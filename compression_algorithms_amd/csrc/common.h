@@ -48,6 +48,9 @@ struct mi_ctx {
     // workspace (device), grown on demand, never inside a captured region
     void       *ws = nullptr;
     size_t      ws_bytes = 0;
+#ifdef MI_TEST_HOOKS
+    size_t      ws_asked = 0;          // lib_test only: the largest request since mi_test_ws_guard's reset (ctx.hip)
+#endif
     // small pinned host staging area for info structs
     void       *h_pinned = nullptr;
     size_t      h_pinned_bytes = 0;
@@ -94,14 +97,32 @@ struct mi_prof_scope {
 
 static inline size_t mi_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// simple carve-out allocator over the workspace
+// Carve-out allocator over the workspace, and the measure of what it carves.  A workspace layout is written ONCE, as a
+// sequence of take() calls; the byte count handed to mi_ws_reserve is bytes() of that same sequence run over no base
+// (measuring: every take hands out nullptr, no pointer is formed).  `limit`: the size of a region that something else owns —
+// a take that ends past it sets `overflow`, for good, and hands out nothing.
 struct mi_carver {
-    uint8_t *base; size_t off = 0;
-    explicit mi_carver(void *b) : base((uint8_t *)b) {}
+    uint8_t *base; size_t limit, off = 0; bool overflow = false;
+    explicit mi_carver(void *b = nullptr, size_t lim = SIZE_MAX) : base((uint8_t *)b), limit(lim) {}
     template <typename T> T *take(size_t count) {
-        off = mi_align_up(off, 256);
-        T *p = (T *)(base + off);
-        off += count * sizeof(T);
-        return p;
+        const size_t at = mi_align_up(off, 256);
+        off = at + count * sizeof(T);
+        if (off > limit) overflow = true;
+        return base && !overflow ? (T *)(base + at) : nullptr;
     }
+    template <typename T> void take(T *&p, size_t count) { p = take<T>(count); }
+    // element i of an array this carver handed out (nothing while it measures)
+    template <typename T> static T *at(T *p, size_t i) { return p ? p + i : nullptr; }
+    size_t bytes() const { return mi_align_up(off, 256); }
 };
+// measure -> reserve -> place: `layout(cv)` takes its arrays from cv; it runs twice, the second time over ctx->ws
+template <typename F> static inline mi_status mi_ws_carve(mi_ctx *ctx, F layout)
+{
+    mi_carver m;
+    layout(m);
+    const mi_status st = mi_ws_reserve(ctx, m.bytes());
+    if (st) return st;
+    mi_carver cv(ctx->ws);
+    layout(cv);
+    return MI_OK;
+}

@@ -263,23 +263,56 @@ int mi_order_poll(mi_ctx *c)
     return 1;
 }
 
+// lib_test only (-DMI_TEST_HOOKS): the allocation's slack hides a layout that overruns its own measure, so the test build
+// turns the slack into a guard — at least MI_WS_GUARD bytes lie behind every request, and mi_test_ws_guard watches them
+#ifdef MI_TEST_HOOKS
+#define MI_WS_GUARD 4096u
+#else
+#define MI_WS_GUARD 0u
+#endif
+
 mi_status mi_ws_reserve(mi_ctx *c, size_t bytes)
 {
-    if (bytes <= c->ws_bytes) return MI_OK;
+#ifdef MI_TEST_HOOKS
+    if (bytes > c->ws_asked) c->ws_asked = bytes;
+#endif
+    if (bytes + MI_WS_GUARD <= c->ws_bytes) return MI_OK;
     // growing frees the old block: only legal while nothing that uses it is in flight
     MI_HIP(c, hipDeviceSynchronize());
     if (c->ws) { MI_HIP(c, hipFree(c->ws)); c->ws = nullptr; c->ws_bytes = 0; }
-    size_t want = mi_align_up(bytes + bytes / 8, 1 << 20);
+    size_t want = mi_align_up(bytes + bytes / 8 + MI_WS_GUARD, 1 << 20);
     if (hipMalloc(&c->ws, want) != hipSuccess) {
         // without the slack; a caller that can work in smaller batches halves its request on MI_ERR_NOMEM (lz_emit.hip)
         (void)hipGetLastError();
-        want = mi_align_up(bytes, 1 << 20);
+        want = mi_align_up(bytes + MI_WS_GUARD, 1 << 20);
         c->ws = nullptr;
         if (hipMalloc(&c->ws, want) != hipSuccess) { (void)hipGetLastError(); c->ws = nullptr; return MI_ERR_NOMEM; }
     }
     c->ws_bytes = want;
     return MI_OK;
 }
+
+#ifdef MI_TEST_HOOKS
+// op 0, reset: forget the largest request.  1, arm: once the device is idle, a byte pattern over [largest request, ws_bytes).
+// 2, check: once the device is idle, -1 if the pattern is whole, else the workspace offset of its first changed byte.
+// -2: a HIP error.  (tests/test_ws_guard_gpu.py)
+extern "C" int64_t mi_test_ws_guard(mi_ctx *c, int op)
+{
+    if (!c || op < 0 || op > 2) return -2;
+    if (op == 0) { c->ws_asked = 0; return -1; }
+    if (hipDeviceSynchronize() != hipSuccess) return -2;
+    const size_t from = c->ws_asked < c->ws_bytes ? c->ws_asked : c->ws_bytes, len = c->ws_bytes - from;
+    uint8_t *d = (uint8_t *)c->ws + from;
+    if (op == 1) return !len || hipMemset(d, 0xA5, len) == hipSuccess ? -1 : -2;
+    uint8_t *h = (uint8_t *)malloc(len ? len : 1);
+    if (!h) return -2;
+    int64_t at = -1;
+    if (len && hipMemcpy(h, d, len, hipMemcpyDeviceToHost) != hipSuccess) at = -2;
+    for (size_t i = 0; at == -1 && i < len; ++i) if (h[i] != 0xA5) at = (int64_t)(from + i);
+    free(h);
+    return at;
+}
+#endif
 
 static hipEvent_t take_event(mi_ctx *c)
 {

@@ -48,7 +48,7 @@ static DfbWs dfb_carve(void *ws, const DfbCall &b)
     w.item_total = cv.take<uint64_t>(b.count);
     w.ck = cv.take<uint32_t>(2 * b.max_blocks);
     w.desc = cv.take<LzBlkDesc>(b.max_blocks);
-    w.bytes = mi_align_up(cv.off, 256);
+    w.bytes = cv.bytes();
     return w;
 }
 

@@ -513,9 +513,10 @@ static_assert(ZCK_GRID <= 1024u, "one combine thread per partial");
 
 size_t defz_ws_bytes() { return 4u * (2u * ZCK_GRID + 64u); }
 
-// partials + combine on `s`; the checksum lands in *d_res.  ws: defz_ws_bytes() of device memory
-static mi_status zck_launch(mi_ctx *ctx, bool crc, const uint8_t *d_in, uint64_t n, uint32_t *ws, uint32_t *d_res, hipStream_t s)
+// partials + combine on `s`; the checksum lands in *d_res.  zws: defz_ws_bytes() of device memory, the caller's to place
+mi_status defz_checksum(mi_ctx *ctx, bool crc, const uint8_t *d_in, uint64_t n, void *zws, uint32_t *d_res, hipStream_t s)
 {
+    uint32_t *ws = (uint32_t *)zws;
     const uint64_t npieces = (n + ZCK_PIECE - 1) / ZCK_PIECE;
     const uint64_t ppg = npieces ? (npieces + ZCK_GRID - 1) / ZCK_GRID : 1;
     const uint32_t grid = (uint32_t)((npieces + ppg - 1) / ppg);
@@ -543,7 +544,7 @@ mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint6
     if (hb) MI_HIP(ctx, hipMemsetAsync(base_bits, (int)(8u * hb), 1, s));             // (<= 80: the low byte)
     if (container == MI_CONTAINER_RAW) return MI_OK;
     uint32_t *ws = (uint32_t *)zws;
-    return zck_launch(ctx, container == MI_CONTAINER_GZIP, d_in, n, ws, ws + ZCK_RESULT_AT, s);
+    return defz_checksum(ctx, container == MI_CONTAINER_GZIP, d_in, n, ws, ws + ZCK_RESULT_AT, s);
 }
 
 __global__ void k_defz_finish(uint8_t *__restrict__ out, uint64_t *__restrict__ block_bits, uint64_t nblocks, uint64_t n,
@@ -601,18 +602,21 @@ extern "C" uint64_t mi_deflate_z_bound_bytes(uint64_t n, const mi_lz_params *p, 
     return (nblocks ? (nblocks - 1) * rec(block) + rec(last) : 0) + c + 2;
 }
 
+// the two checksums as entry points: the partials in a workspace of their own
+static mi_status zck_dev(mi_ctx *ctx, bool crc, const uint8_t *d_in, uint64_t n, uint32_t *d_res, void *stream)
+{
+    if (!ctx || !d_res || (n && !d_in)) return MI_ERR_ARG;
+    uint8_t *zws;
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(zws, defz_ws_bytes()); });
+    return st ? st : defz_checksum(ctx, crc, d_in, n, zws, d_res, (hipStream_t)stream);
+}
+
 extern "C" mi_status mi_crc32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_crc, void *stream)
 {
-    if (!ctx || !d_crc || (n && !d_in)) return MI_ERR_ARG;
-    mi_status st = mi_ws_reserve(ctx, defz_ws_bytes());
-    if (st) return st;
-    return zck_launch(ctx, true, d_in, n, (uint32_t *)ctx->ws, d_crc, (hipStream_t)stream);
+    return zck_dev(ctx, true, d_in, n, d_crc, stream);
 }
 
 extern "C" mi_status mi_adler32_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_adler, void *stream)
 {
-    if (!ctx || !d_adler || (n && !d_in)) return MI_ERR_ARG;
-    mi_status st = mi_ws_reserve(ctx, defz_ws_bytes());
-    if (st) return st;
-    return zck_launch(ctx, false, d_in, n, (uint32_t *)ctx->ws, d_adler, (hipStream_t)stream);
+    return zck_dev(ctx, false, d_in, n, d_adler, stream);
 }

@@ -567,12 +567,9 @@ extern "C" mi_status mi_fse_encode_dev(mi_ctx *ctx, const mi_fse_params *p, cons
     if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_offsets, 0, 8, s)); return MI_OK; }
     // scratch records: fixed part + 64 lanes at a fixed stride (fse.hip header); 256-byte aligned stride
     const uint64_t scr_stride = mi_align_up((size_t)FSE_SCR_FIXED + (size_t)FSE_MAX_S * fse_lane_stride_words(P.block, P.S, P.L) * 4u, 256);
-    st = mi_ws_reserve(ctx, nblocks * scr_stride + (nblocks + 2) * 12 + 8192);
+    uint8_t *recs; uint64_t *bits; uint32_t *fixed;
+    st = mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(recs, nblocks * scr_stride); cv.take(bits, nblocks + 1); cv.take(fixed, nblocks + 1); });
     if (st) return st;
-    mi_carver cv(ctx->ws);
-    uint8_t *recs = cv.take<uint8_t>(nblocks * scr_stride);
-    uint64_t *bits = cv.take<uint64_t>(nblocks + 1);
-    uint32_t *fixed = cv.take<uint32_t>(nblocks + 1);
     {
         mi_prof_scope pr(ctx, "k_fse_encode", s, n);
         hipLaunchKernelGGL(k_fse_encode, dim3((unsigned)nblocks), dim3(64), 3u << P.L, s, d_in, n, P, recs, scr_stride, bits, fixed);

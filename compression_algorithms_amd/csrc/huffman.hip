@@ -336,11 +336,23 @@ void k_huff_encode(const uint8_t *__restrict__ in, uint64_t n, const uint32_t *_
 // ---------------------------------------------------------------------------------------------
 static inline uint64_t huff_ntiles(uint64_t n) { return (n + HUFF_TILE - 1) / HUFF_TILE; }
 
-// workspace of mi_huffman_encode_dev over n bytes (host_api.hip reserves it before it queues anything)
+// workspace of mi_huffman_encode_dev over ntiles tiles
+struct HuffWs { uint32_t *hist, *code; uint8_t *len; uint32_t *tile_hist; uint64_t *tile_bits, *tile_off; };
+static void huff_carve(mi_carver &cv, uint64_t ntiles, HuffWs *w)
+{
+    w->hist = cv.take<uint32_t>(256);
+    w->code = cv.take<uint32_t>(256);
+    w->len = cv.take<uint8_t>(256);
+    w->tile_hist = cv.take<uint32_t>((ntiles ? ntiles : 1) * 256);
+    w->tile_bits = cv.take<uint64_t>(ntiles + 1);
+    w->tile_off = cv.take<uint64_t>(ntiles + 2);
+}
+// ... in bytes, over n bytes (host_api.hip reserves it before it queues anything)
 size_t huff_ws_bytes(uint64_t n)
 {
-    const uint64_t ntiles = huff_ntiles(n);
-    return 256 * 4 + 256 * 4 + 256 + ntiles * 1024 + (ntiles + 1) * 8 * 2 + 4096;
+    mi_carver cv; HuffWs w;
+    huff_carve(cv, huff_ntiles(n), &w);
+    return cv.bytes();
 }
 
 extern "C" mi_status mi_huffman_encode_dev(mi_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_words,
@@ -351,15 +363,12 @@ extern "C" mi_status mi_huffman_encode_dev(mi_ctx *ctx, const uint8_t *d_in, uin
     if (((uintptr_t)d_in & 15) != 0) return MI_ERR_ARG;        // 16-B loads
     hipStream_t s = (hipStream_t)stream;   // NULL = HIP's default stream
     const uint64_t ntiles = huff_ntiles(n);
-    const size_t need = huff_ws_bytes(n);
-    if (need > ctx->ws_bytes) { mi_status st = mi_ws_reserve(ctx, need); if (st) return st; }
-    mi_carver cv(ctx->ws);
-    uint32_t *hist = cv.take<uint32_t>(256);
-    uint32_t *code = cv.take<uint32_t>(256);
-    uint8_t  *len = cv.take<uint8_t>(256);
-    uint32_t *tile_hist = cv.take<uint32_t>((ntiles ? ntiles : 1) * 256);
-    uint64_t *tile_bits = cv.take<uint64_t>(ntiles + 1);
-    uint64_t *tile_off = cv.take<uint64_t>(ntiles + 2);
+    HuffWs w;
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) { huff_carve(cv, ntiles, &w); });
+    if (st) return st;
+    uint32_t *hist = w.hist, *code = w.code, *tile_hist = w.tile_hist;
+    uint8_t  *len = w.len;
+    uint64_t *tile_bits = w.tile_bits, *tile_off = w.tile_off;
     MI_HIP(ctx, hipMemsetAsync(hist, 0, 256 * 4, s));
     if (ntiles) {
         mi_prof_scope p(ctx, "k_huff_hist", s, n);
@@ -420,12 +429,9 @@ extern "C" mi_status mi_huffman_build_dev(mi_ctx *ctx, const uint64_t *d_hist, m
 {
     if (!ctx || !d_hist || !d_info || !d_tree) return MI_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    size_t need = 256 * 4 + 256 * 4 + 256 + 4096;
-    if (need > ctx->ws_bytes) { mi_status st = mi_ws_reserve(ctx, need); if (st) return st; }
-    mi_carver cv(ctx->ws);
-    uint32_t *hist = cv.take<uint32_t>(256);
-    uint32_t *code = cv.take<uint32_t>(256);
-    uint8_t  *len = cv.take<uint8_t>(256);
+    uint32_t *hist, *code; uint8_t *len;
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(hist, 256); cv.take(code, 256); cv.take(len, 256); });
+    if (st) return st;
     hipLaunchKernelGGL(k_huff_hist_narrow, dim3(1), dim3(256), 0, s, d_hist, hist);
     {
         mi_prof_scope p(ctx, "k_huff_build", s, 1024);
@@ -443,12 +449,9 @@ extern "C" mi_status mi_huffman_encode_with_tree_dev(mi_ctx *ctx, const uint8_t 
     if (((uintptr_t)d_in & 15) != 0 || ((uintptr_t)d_tile_hist & 15) != 0) return MI_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const uint64_t ntiles = huff_ntiles(n);
-    size_t need = (ntiles + 1) * 8 * 2 + 4096;
-    if (need > ctx->ws_bytes) { mi_status st = mi_ws_reserve(ctx, need); if (st) return st; }
-    mi_carver cv(ctx->ws);
-    uint64_t *tile_bits = cv.take<uint64_t>(ntiles + 1);
-    uint64_t *tile_off = cv.take<uint64_t>(ntiles + 2);
-    uint32_t *uncovered = cv.take<uint32_t>(4);
+    uint64_t *tile_bits, *tile_off; uint32_t *uncovered;
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(tile_bits, ntiles + 1); cv.take(tile_off, ntiles + 2); cv.take(uncovered, 4); });
+    if (st) return st;
     const uint32_t *code = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(d_tree) + offsetof(mi_huffman_tree, code));
     const uint8_t *len = reinterpret_cast<const uint8_t *>(d_tree) + offsetof(mi_huffman_tree, length);
     // the caller's info is rewritten for THIS shard: status OK, sizes of bit_offset + shard bits

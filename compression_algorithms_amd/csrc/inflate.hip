@@ -30,6 +30,7 @@
 // status words behind the checksum partials in the context workspace
 #define INF_WS_CK    0u                        // the checksum of the decoded bytes
 #define INF_WS_FINAL 1u                        // set by k_inflate: the (only) segment ended with its BFINAL = 1 block
+#define INF_WS_WORDS 2u
 
 // DESC (BGZF, bgzf.hip): `seg_bits` points at one InfSeg descriptor per segment instead of the table — the segment's first
 // and last bit, output offset and output length; block, nseg and n_total are not used.  Every segment is a whole DEFLATE
@@ -147,11 +148,10 @@ extern "C" mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t bl
     const uint64_t nseg = (n + block - 1) / block;
     if (nseg > 0x7FFFFFFFull) return MI_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const size_t ck_bytes = mi_align_up(defz_ws_bytes(), 256);
-    mi_status st = mi_ws_reserve(ctx, ck_bytes + 256);
+    uint8_t *zws; uint32_t *status;                      // the checksum's partials, then the status words
+    mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(zws, defz_ws_bytes()); cv.take(status, INF_WS_WORDS); });
     if (st) return st;
-    uint32_t *status = (uint32_t *)((uint8_t *)ctx->ws + ck_bytes);
-    MI_HIP(ctx, hipMemsetAsync(status, 0, 8, s));
+    MI_HIP(ctx, hipMemsetAsync(status, 0, INF_WS_WORDS * 4, s));
     uint32_t *err = mi_err_slot(ctx, s);
     if (!err) return MI_ERR_HIP;
     if (nseg) {
@@ -165,7 +165,7 @@ extern "C" mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t bl
         if (hipGetLastError() != hipSuccess) return MI_ERR_HIP;
     }
     if (container != MI_CONTAINER_RAW && !(flags & MI_INFLATE_NO_CHECKSUM)) {
-        st = container == MI_CONTAINER_GZIP ? mi_crc32_dev(ctx, d_out, n, status + INF_WS_CK, s) : mi_adler32_dev(ctx, d_out, n, status + INF_WS_CK, s);
+        st = defz_checksum(ctx, container == MI_CONTAINER_GZIP, d_out, n, zws, status + INF_WS_CK, s);
         if (st) return st;
     }
     hipLaunchKernelGGL(k_inflate_frame, dim3(1), dim3(64), 0, s, d_stream, stream_bytes, d_seg_bits, nseg, n, container, flags, status, err);

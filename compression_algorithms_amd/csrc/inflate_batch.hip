@@ -169,13 +169,13 @@ static mi_status batch_launch(mi_ctx *ctx, uint32_t container, uint64_t count, c
     // its memset and three launches (DESIGN_HISTORY.md): by default workgroup j takes item j and no workspace is touched.
     const char *e = getenv("MI_INFLATE_BATCH_ORDER");
     const bool ordered = e && atoi(e) != 0;
-    mi_status st = ordered ? mi_ws_reserve(ctx, INFB_WS_HEAD + 4ull * cnt) : MI_OK;   // (allocates and synchronises only while it grows)
+    uint32_t *head = nullptr, *order = nullptr;              // head: hist[64], cursor[64]
+    const mi_status st = ordered ? mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(head, INFB_WS_HEAD / 4); cv.take(order, cnt); })
+                                 : MI_OK;                    // (allocates and synchronises only while it grows)
     if (st) return st;
     if (d_failed) MI_HIP(ctx, hipMemsetAsync(d_failed, 0, 4, s));
-    uint32_t *order = nullptr;
     if (ordered) {
-        uint32_t *hist = (uint32_t *)ctx->ws, *cursor = hist + 64;
-        order = (uint32_t *)((uint8_t *)ctx->ws + INFB_WS_HEAD);
+        uint32_t *hist = head, *cursor = hist + 64;
         MI_HIP(ctx, hipMemsetAsync(hist, 0, INFB_WS_HEAD, s));
         mi_prof_scope pr(ctx, "k_batch_order", s, 0);
         hipLaunchKernelGGL(k_batch_hist, dim3((cnt + 255u) / 256u), dim3(256), 0, s, d_in_bytes, cnt, hist);

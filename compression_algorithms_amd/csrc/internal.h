@@ -7,13 +7,12 @@
 #include "lz_common.h"               // LzP, LzScratch, LzwScratch
 #include "lz2.h"                     // Lz2Scratch
 
-// ---- huffman.hip: the workspace of mi_huffman_encode_dev over n bytes
+// ---- huffman.hip: the workspace of mi_huffman_encode_dev over n bytes (the measure of its carve)
 size_t    huff_ws_bytes(uint64_t n);
 
 // ---- lz_find.hip: parameters, workspace and the stages of the match finder
 mi_status lz_check_params(const mi_lz_params *p);
-size_t    lz_scratch_bytes(uint32_t nb);
-void      lz_carve(mi_ctx *ctx, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2, int set);
+void      lz_carve(mi_carver &cv, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2);            // one scratch set; sets are multiples of 4096
 uint32_t  lz_batch_blocks(mi_ctx *ctx, uint64_t nblocks);
 bool      lz_use_v2();
 mi_status lz_find_stage_a(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
@@ -23,7 +22,6 @@ mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scrat
 
 // ---- lz2_partition.hip, lz2_find.hip: the LDS-resident finder
 void      lz2_launch_partition(const uint8_t *d_in, uint64_t n, const LzP &P, const Lz2Scratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
-size_t    lz2_scratch_bytes(uint32_t nb);
 void      lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc);
 mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                               const Lz2Scratch &sc, hipStream_t s);
@@ -35,8 +33,7 @@ mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &
 void      lz2_launch_scatter(const Lz2Scratch &sc, uint16_t *cand_by_pos, uint32_t nb, hipStream_t s);
 
 // ---- lzw.hip: the lz77 flavour on blocks above 64 KiB
-size_t    lzw_scratch_bytes(uint32_t nb, uint32_t block);
-void      lzw_carve(mi_ctx *ctx, uint32_t nb, uint32_t block, LzwScratch *sc);
+mi_status lzw_reserve(mi_ctx *ctx, uint32_t *nb, uint32_t block, LzwScratch *sc, uint64_t **base_bits);   // measures, halves *nb on MI_ERR_NOMEM, places
 uint32_t  lzw_batch_blocks(mi_ctx *ctx, uint64_t nblocks, uint32_t block);
 mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s);
 void      lzw_launch_parse_emit(const uint8_t *d_in, uint64_t n, const LzP &P, const LzwScratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
@@ -66,6 +63,7 @@ void      defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *bl
 uint32_t  defz_header_bytes(uint32_t container);
 uint32_t  defz_trailer_bytes(uint32_t container);
 size_t    defz_ws_bytes();                                             // the checksum partials
+mi_status defz_checksum(mi_ctx *ctx, bool crc, const uint8_t *d_in, uint64_t n, void *zws, uint32_t *d_res, hipStream_t s);   // zws: those
 mi_status defz_check(const mi_lz_params *p, uint32_t container);
 mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t *base_bits,
                      void *zws, hipStream_t s);

@@ -1241,14 +1241,6 @@ static uint32_t lz2_class_cap(uint32_t c)
     return LZ_MAX_BLOCK / lo[c] + 8;
 }
 
-size_t lz2_scratch_bytes(uint32_t nb)
-{
-    size_t descs = 0;                                    // what lz2_carve takes for the class descriptor arrays, exactly
-    for (uint32_t c = 0; c < LZ2_NCLASS; ++c) descs += lz2_class_cap(c);
-    return (size_t)nb * (LZ_MAX_BLOCK * (2 * 2 + 1) + LZ2_BIG_STRIDE * 2 * 4 + sizeof(Lz2BlockMeta) + 4 + 8 * LZ2_MAXPARTS + descs * sizeof(Lz2BigDesc)
-                         + lz2_class_cap(7) * sizeof(uint4)) + 16 * 256 + 4096 + 64 * 256 + 2 * LANE_SIZES * 4 + 256;
-}
-
 void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
 {
     sc->partmap = cv.take<uint8_t>((size_t)nb * LZ_MAX_BLOCK);
@@ -1262,9 +1254,9 @@ void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
     sc->bigpid = cv.take<uint16_t>((size_t)nb * LZ2_BIG_STRIDE);
     sc->bigcand = cv.take<uint16_t>((size_t)nb * LZ2_BIG_STRIDE);
     for (uint32_t c = 0; c < LZ2_NCLASS; ++c) sc->desc[c] = cv.take<Lz2BigDesc>((size_t)nb * lz2_class_cap(c));
-    sc->big_count = sc->fallback_count + 16;
-    sc->work_count = sc->fallback_count + 32;            // zeroed with the other counters by stage 1
-    sc->lane_hist = sc->fallback_count + 64;             // (as are these)
+    sc->big_count = cv.at(sc->fallback_count, 16);
+    sc->work_count = cv.at(sc->fallback_count, 32);      // zeroed with the other counters by stage 1
+    sc->lane_hist = cv.at(sc->fallback_count, 64);       // (as are these)
     sc->work = cv.take<uint64_t>((size_t)nb * LZ2_MAXPARTS);
     sc->work_slots = nb * LZ2_MAXPARTS;
     sc->lane_list = cv.take<uint4>((size_t)nb * lz2_class_cap(7));

@@ -537,14 +537,10 @@ __device__ __forceinline__ uint32_t stream_bits(const uint8_t *s, uint64_t nbyte
 static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
                                 uint64_t *d_block_bits, uint64_t nblocks, hipStream_t s)
 {
-    mi_status st;
     uint32_t nbw = lzw_batch_blocks(ctx, nblocks, P.block);
-    // (a workspace the context already holds is reused whatever its size; a batch that does not fit is halved)
-    while ((st = mi_ws_reserve(ctx, lzw_scratch_bytes(nbw, P.block) + 4096)) == MI_ERR_NOMEM && nbw > 1) nbw = (nbw + 1) / 2;
+    LzwScratch ws; uint64_t *base_bits_w;
+    mi_status st = lzw_reserve(ctx, &nbw, P.block, &ws, &base_bits_w);
     if (st) return st;
-    LzwScratch ws;
-    lzw_carve(ctx, nbw, P.block, &ws);
-    uint64_t *base_bits_w = reinterpret_cast<uint64_t *>((uint8_t *)ctx->ws + lzw_scratch_bytes(nbw, P.block));
     MI_HIP(ctx, hipMemsetAsync(base_bits_w, 0, 8, s));
     if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return MI_OK; }
     for (uint64_t b0 = 0; b0 < nblocks; b0 += nbw) {
@@ -564,19 +560,16 @@ static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, 
     return MI_OK;
 }
 
-// the workspace behind the scratch sets (lz_carve): the output's running bit position, the token records of every form but
-// LZ_TOKENS (one array per set), and what the form keeps for itself (mode Z: the checksum's partials; a batch: its tables)
-struct LzTail { uint64_t *base_bits; uint32_t *trec; void *zws; size_t bytes; };                // bytes: sets and tail together
+// The pipeline's workspace: the scratch sets (lz_carve), then the output's running bit position, the token records of every
+// form but LZ_TOKENS (one array per set), and what the form keeps for itself (mode Z: the checksum's partials; a batch: its tables)
+struct LzWs { LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS]; uint64_t *base_bits; uint32_t *trec; void *zws; };
 
-static LzTail lz_carve_tail(void *ws, size_t sets_bytes, size_t trec_words, size_t z_bytes)
+static void lz_carve_all(mi_carver &cv, uint32_t nb, int nsets, size_t trec_words, size_t z_bytes, LzWs *w)
 {
-    mi_carver cv((uint8_t *)ws + sets_bytes);
-    LzTail t;
-    t.base_bits = reinterpret_cast<uint64_t *>(cv.take<uint8_t>(8192));
-    t.trec = trec_words ? cv.take<uint32_t>(trec_words) : nullptr;
-    t.zws = cv.take<uint8_t>(z_bytes);
-    t.bytes = sets_bytes + cv.off;
-    return t;
+    for (int k = 0; k < nsets; ++k) lz_carve(cv, nb, &w->sc[k], &w->sc2[k]);
+    w->base_bits = reinterpret_cast<uint64_t *>(cv.take<uint8_t>(8192));
+    w->trec = trec_words ? cv.take<uint32_t>(trec_words) : nullptr;
+    w->zws = cv.take<uint8_t>(z_bytes);
 }
 
 // The stream of the fallback chains of the ODD batches of a pipelined call (the even ones' is ctx->fb); creates or releases
@@ -656,14 +649,12 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
     // plus ctx->fb for the normally empty fallback chain.  Fork/join with events only: no host synchronisation.
     const bool overlap = nblocks > nbmax && !getenv("MI_LZ_NO_OVERLAP");
     const int nsets = overlap ? MI_SETS : 1;
-    const size_t sets_bytes = mi_align_up(lz_scratch_bytes(nbmax), 4096) * nsets;
     const size_t trec_words = c.form == LZ_TOKENS ? 0 : (size_t)nbmax * LZ_MAX_BLOCK * nsets;
     const size_t z_bytes = items ? dfb_ws_bytes(*c.batch) : (c.form == LZ_Z || c.form == LZ_BGZF) ? defz_ws_bytes() : 0;
-    st = mi_ws_reserve(ctx, lz_carve_tail(nullptr, sets_bytes, trec_words, z_bytes).bytes);
+    LzWs t;
+    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve_all(cv, nbmax, nsets, trec_words, z_bytes, &t); });
     if (st) return st;
-    LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS];
-    for (int k = 0; k < nsets; ++k) lz_carve(ctx, nbmax, &sc[k], &sc2[k], k);
-    const LzTail t = lz_carve_tail(ctx->ws, sets_bytes, trec_words, z_bytes);
+    const LzScratch *sc = t.sc; const Lz2Scratch *sc2 = t.sc2;
     // in front of the first block: where the output's bits start, and what the form needs before its blocks
     switch (c.form) {
     case LZ_TOKENS: case LZ_H: MI_HIP(ctx, hipMemsetAsync(t.base_bits, 0, 8, s)); break;

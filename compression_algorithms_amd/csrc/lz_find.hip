@@ -768,22 +768,16 @@ void k_lz_emulate_dom(LzP P, LzScratch sc, uint64_t *dbg)
 // =============================================================================================
 // host side of the match finder
 // =============================================================================================
-size_t lz_scratch_bytes(uint32_t nb)
-{
-    size_t per = (size_t)LZ_MAX_BLOCK * (2 + 2 + 8 + 8 + 2) + sizeof(LzBlockMeta) + LZ_MAX_GIANTS_PER_BLOCK * 8 +
-                 (size_t)LZ_SLOT_WORDS * 4 + 8;
-    return per * nb + 16 * 256 + 4096 + lz2_scratch_bytes(nb) + 64 * 256;
-}
-
 bool lz_use_v2()
 {
     const char *e = getenv("MI_LZ_V2");
     return !(e && e[0] == '0');
 }
 
-void lz_carve(mi_ctx *ctx, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2, int set)
+// one scratch set of nb blocks, both finders' arrays; sets start and end on multiples of 4096, so a call's sets are one stride apart
+void lz_carve(mi_carver &cv, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2)
 {
-    mi_carver cv((uint8_t *)ctx->ws + (size_t)set * mi_align_up(lz_scratch_bytes(nb), 4096));
+    cv.off = mi_align_up(cv.off, 4096);
     sc->posA = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
     sc->posB = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
     sc->eA = cv.take<uint64_t>((size_t)nb * LZ_MAX_BLOCK);
@@ -795,7 +789,8 @@ void lz_carve(mi_ctx *ctx, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2, int set)
     sc->giant_cap = nb * LZ_MAX_GIANTS_PER_BLOCK;
     sc->slot = cv.take<uint32_t>((size_t)nb * LZ_SLOT_WORDS);
     sc->block_bits = cv.take<uint64_t>(nb + 1);
-    if (sc2) lz2_carve(cv, nb, sc2);
+    lz2_carve(cv, nb, sc2);
+    cv.off = mi_align_up(cv.off, 4096);
 }
 
 mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
@@ -940,10 +935,9 @@ extern "C" mi_status mi_lz_find_all_dev(mi_ctx *ctx, const mi_lz_params *p, cons
     const LzP P = lz_params_of(ctx, p);
     const uint64_t nblocks = (n + P.block - 1) / P.block;
     const uint32_t nbmax = lz_batch_blocks(ctx, nblocks);
-    st = mi_ws_reserve(ctx, lz_scratch_bytes(nbmax));
-    if (st) return st;
     LzScratch sc; Lz2Scratch sc2;
-    lz_carve(ctx, nbmax, &sc, &sc2, 0);
+    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve(cv, nbmax, &sc, &sc2); });
+    if (st) return st;
     for (uint64_t b0 = 0; b0 < nblocks; b0 += nbmax) {
         const uint32_t nb = (uint32_t)((nblocks - b0) < nbmax ? (nblocks - b0) : nbmax);
         st = lz_run_find(ctx, P, d_in, n, b0, nb, sc, sc2, s);
@@ -972,10 +966,9 @@ extern "C" mi_status mi_lz_find_all32_dev(mi_ctx *ctx, const mi_lz_params *p, co
     const LzP P = lz_params_of(ctx, p);
     const uint64_t nblocks = (n + P.block - 1) / P.block;
     uint32_t nbw = lzw_batch_blocks(ctx, nblocks, P.block);
-    while ((st = mi_ws_reserve(ctx, lzw_scratch_bytes(nbw, P.block) + 4096)) == MI_ERR_NOMEM && nbw > 1) nbw = (nbw + 1) / 2;
-    if (st) return st;
     LzwScratch ws;
-    lzw_carve(ctx, nbw, P.block, &ws);
+    st = lzw_reserve(ctx, &nbw, P.block, &ws, nullptr);
+    if (st) return st;
     for (uint64_t b0 = 0; b0 < nblocks; b0 += nbw) {
         const uint32_t nb = (uint32_t)((nblocks - b0) < nbw ? (nblocks - b0) : nbw);
         st = lzw_or_lzs_find(ctx, P, d_in, n, b0, nb, ws, s);

@@ -165,19 +165,16 @@ extern "C" mi_status mi_lz77_old_encode_dev(mi_ctx *ctx, uint32_t wbits, uint32_
     if (wbits < 8 || wbits > 16 || lbits < 3 || lbits > 5) return MI_ERR_ARG;
     if (cap_bytes < mi_lz77_old_bound_bytes(n)) return MI_ERR_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
-    MI_HIP(ctx, hipMemsetAsync(d_out, 0, mi_lz77_old_bound_bytes(n), s));
-    if (n == 0) { MI_HIP(ctx, hipMemsetAsync(d_total_bits, 0, 8, s)); return MI_OK; }
+    if (n == 0) { MI_HIP(ctx, hipMemsetAsync(d_out, 0, mi_lz77_old_bound_bytes(n), s)); MI_HIP(ctx, hipMemsetAsync(d_total_bits, 0, 8, s)); return MI_OK; }
     const uint64_t nchunks = (n + 63) / 64, nsuper = (nchunks + 63) / 64;
     // workspace: L n | O 2n | ex 32 per chunk | sx 32 per super | sentry | entry | chunk_bits | chunk_off
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = mi_align_up(off + bytes, 256); return o; };
-    const size_t oL = take(n), oO = take(2 * n), oex = take(nchunks * LZOLD_ENT), osx = take(nsuper * LZOLD_ENT), ose = take(nsuper),
-                 oen = take(nchunks), ocb = take(8 * nchunks), oco = take(8 * (nchunks + 1));
-    mi_status st = mi_ws_reserve(ctx, off);
+    uint8_t *L, *ex, *sx, *sentry, *entry; uint16_t *O; uint64_t *cb, *co;
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) {
+        cv.take(L, n); cv.take(O, n); cv.take(ex, nchunks * LZOLD_ENT); cv.take(sx, nsuper * LZOLD_ENT); cv.take(sentry, nsuper);
+        cv.take(entry, nchunks); cv.take(cb, nchunks); cv.take(co, nchunks + 1);
+    });
     if (st) return st;
-    uint8_t *ws = (uint8_t *)ctx->ws;
-    uint8_t *L = ws + oL; uint16_t *O = (uint16_t *)(ws + oO); uint8_t *ex = ws + oex, *sx = ws + osx, *sentry = ws + ose, *entry = ws + oen;
-    uint64_t *cb = (uint64_t *)(ws + ocb), *co = (uint64_t *)(ws + oco);
+    MI_HIP(ctx, hipMemsetAsync(d_out, 0, mi_lz77_old_bound_bytes(n), s));
     const uint32_t max_len = (1u << lbits) - 1u, WS = (1u << wbits) - 1u;
     const size_t lds = (size_t)WS + LZOLD_TILE + 48;
     {
@@ -206,13 +203,13 @@ extern "C" mi_status mi_lz77_whole_decode_dev(mi_ctx *ctx, uint32_t wbits, uint3
     if (total_bits > stream_bytes * 8) return MI_ERR_CORRUPT;
     if (n == 0) return MI_OK;
     hipStream_t s = (hipStream_t)stream;
-    mi_status st = mi_ws_reserve(ctx, 64);
+    uint64_t *d_bits;                                            // the table of the one block: {0, total_bits}
+    const mi_status st = mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(d_bits, 2); });
     if (st) return st;
     mi_lz_params p = mi_lz_params_lz77(wbits);
     p.lbits = lbits;
     LzP P = lz_params_of(ctx, &p);
     P.block = (uint32_t)n;                                       // the buffer is the block
-    uint64_t *d_bits = reinterpret_cast<uint64_t *>(ctx->ws);
     const uint64_t h_bits[2] = {0, total_bits};
     MI_HIP(ctx, hipMemcpyAsync(d_bits, h_bits, 16, hipMemcpyHostToDevice, s));
     uint32_t *err = mi_err_slot(ctx, s);

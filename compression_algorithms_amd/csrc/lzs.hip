@@ -1041,20 +1041,28 @@ void k_lzs_big(LzP P, LzsScratch sc, uint32_t step, uint32_t cls)
 // =============================================================================================
 // host side
 // =============================================================================================
-void lzs_view(const LzwScratch &ws, uint32_t nb, LzsScratch *sc)
+// The sliced finder lives in the arrays of lzw.hip's workspace (which it never uses at the same time): most as they are, its own
+// records carved inside eA and eB (nb x S x 8 bytes each).  *zero_bytes: what a batch zeroes from `counters` on — the counters
+// and the debug counters, not the flag list behind them.  false: a region is too small for what is carved in it.
+static bool lzs_view(const LzwScratch &ws, const LzP &P, uint32_t nb, LzsScratch *sc, size_t *zero_bytes)
 {
-    // the sliced finder lives in the arrays of lzw.hip's workspace (which it never uses at the same time)
     sc->key = ws.gid; sc->slot = ws.rd; sc->cand = ws.cand; sc->plist = ws.t_pos; sc->S = ws.S;
-    sc->meta = reinterpret_cast<LzsMeta *>(ws.eA);                       // nb records at the start of the nb x S x 8 B of eA ...
-    sc->pmap = reinterpret_cast<uint8_t *>(ws.eA) + mi_align_up((size_t)nb * sizeof(LzsMeta), 256);   // ... then nb part maps of 2 W <= 128 KiB (S >= 65 792: 8 S bytes per block)
-    sc->work = reinterpret_cast<uint64_t *>(ws.eB);                      // nb x 64 items
-    sc->counters = reinterpret_cast<uint32_t *>(sc->work + (size_t)nb * LZS_MAXPARTS);                 // four groups x LZS_CTR_WORDS ([64] of the first: flagged blocks)
-    sc->flag_count = sc->counters + 64;
-    sc->flag_list = sc->counters + 4 * LZS_CTR_WORDS + 64;               // behind the debug counters: one word per block
+    const size_t region = (size_t)nb * ws.S * 8;
+    mi_carver a(ws.eA, region), b(ws.eB, region);
+    sc->meta = a.take<LzsMeta>(nb);
+    sc->pmap = a.take<uint8_t>((size_t)nb * 2u << P.wbits);              // a part map of 2 W bytes per block
+    sc->work = b.take<uint64_t>((size_t)nb * LZS_MAXPARTS);
+    const size_t counters_at = mi_align_up(b.off, 256);
+    sc->counters = b.take<uint32_t>(4 * LZS_CTR_WORDS);                  // four groups ([64] of the first: flagged blocks)
+    uint64_t *dbg = b.take<uint64_t>(32);
+    *zero_bytes = b.off - counters_at;
+    sc->flag_list = b.take<uint32_t>(nb);                                // one word per block
+    sc->flag_count = mi_carver::at(sc->counters, 64);
     sc->lb0 = 0;
-    sc->dbg = getenv("MI_LZ_DEBUG") ? reinterpret_cast<uint64_t *>(sc->counters + 4 * LZS_CTR_WORDS) : nullptr;
+    sc->dbg = getenv("MI_LZ_DEBUG") ? dbg : nullptr;
     sc->big_key = ws.t_mix; sc->big_info = ws.slot_of;                   // nb x S words each: a step has at most nb x S events
     for (uint32_t q = 0; q < LZS_NCLS; ++q) sc->big_desc[q] = ws.clist[q];  // nb x S / 2 + 64 each (a cluster has >= 17 events)
+    return !a.overflow && !b.overflow;
 }
 
 // at most 64 steps per block (their work counters), event ids below 2^17; MI_LZW_SLICED=0 keeps lzw.hip's whole-block path (A/B, tests)
@@ -1074,10 +1082,9 @@ bool lzs_applicable(const LzP &P)
 mi_status lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                    const LzwScratch &ws, hipStream_t s, uint32_t *flagged, const uint32_t **flag_list)
 {
-    static_assert(sizeof(LzsMeta) + 2u * 65536u + 512u <= 65792u * 8u, "meta records and part maps live in eA: 8 S bytes per block, S >= 65 792");
     if (!lzs_applicable(P)) return MI_ERR_ARG;
-    LzsScratch all;
-    lzs_view(ws, nb, &all);
+    LzsScratch all; size_t zero_bytes;
+    if (!lzs_view(ws, P, nb, &all, &zero_bytes)) return MI_ERR_ARG;
     const uint32_t W = 1u << P.wbits;
     const uint32_t nsteps = (P.block + W - 1u) / W;
     const uint32_t chunks = (P.block + 256u * 16u - 1u) / (256u * 16u);
@@ -1086,7 +1093,7 @@ mi_status lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, u
     const bool multi = ctx->side && ctx->parse && ctx->fb && !getenv("MI_LZS_SERIAL");       // MI_LZS_SERIAL=1: one stream (per-kernel times)
     hipStream_t st[2] = {s, multi ? ctx->side : s}, ax[2] = {multi ? ctx->parse : s, multi ? ctx->fb : s};
     const uint32_t G = (nb < 2u || !multi) ? 1u : 2u;
-    MI_HIP(ctx, hipMemsetAsync(all.counters, 0, (size_t)LZS_CTR_WORDS * 4 * 4 + 32 * 8, s));      // counters of four groups + the 32 debug counters (the flag list lies behind them)
+    MI_HIP(ctx, hipMemsetAsync(all.counters, 0, zero_bytes, s));
     MI_HIP(ctx, hipEventRecord(ctx->ev_fork, s));
     LzsScratch sg[2]; uint32_t lo[3];
     for (uint32_t g = 0; g <= G; ++g) lo[g] = (uint32_t)(((uint64_t)nb * g) / G);

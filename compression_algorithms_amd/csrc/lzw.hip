@@ -670,31 +670,49 @@ void k_lzw_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, L
 // =============================================================================================
 // host side
 // =============================================================================================
-size_t lzw_scratch_bytes(uint32_t nb, uint32_t block)
+// The wide layout, once: every array of LzwScratch in workspace order as f(array, elements per block, elements beside them,
+// rows) — rows: a block has rows of its own there (lzw_view_at); the class lists and their counters belong to the batch.
+template <typename F> static void lzw_arrays(LzwScratch &sc, F f)
 {
-    const size_t S = mi_align_up(block, 256);
-    return (size_t)nb * (S * (8 + 8 + 4 + 4 + 4 + 4 + 4 + 4 + 4 + 4 + 4 + 2 + 24) + (S + 64) + 8 * 4 + 16 + (size_t)LZW_SLOT_WORDS(block) * 4 + 8 + 4096) + 65536;
+    const size_t S = sc.S;
+    f(sc.eA, S, 0, true); f(sc.eB, S, 0, true); f(sc.gid, S, 0, true); f(sc.rd, S, 0, true);
+    f(sc.cstart, S + 2, 0, true); f(sc.ncl, 4, 0, true); f(sc.t_live, S + 64, 0, true);
+    f(sc.t_pos, S, 0, true); f(sc.t_mix, S, 0, true); f(sc.slot_of, S, 0, true); f(sc.cand, S, 0, true);
+    f(sc.ent, S, 0, true); f(sc.relw, S, 0, true); f(sc.cand_e, S, 0, true);
+    for (int c = 0; c < 6; ++c) f(sc.clist[c], S / 2, 64, false);
+    f(sc.ccount, 0, 64, false);
+    f(sc.slot, sc.slot_words, 0, true); f(sc.block_bits, 1, 1, true);
 }
 
-void lzw_carve(mi_ctx *ctx, uint32_t nb, uint32_t block, LzwScratch *sc)
+// ... and behind them the running bit position of the encoder's output (lz_emit.hip; *base_bits may be NULL: the find hook)
+static void lzw_carve(mi_carver &cv, uint32_t nb, uint32_t block, LzwScratch *sc, uint64_t **base_bits)
 {
+    sc->S = (uint32_t)mi_align_up(block, 256); sc->slot_words = LZW_SLOT_WORDS(block);
+    lzw_arrays(*sc, [&](auto *&p, size_t per, size_t beside, bool) { cv.take(p, nb * per + beside); });
+    uint64_t *bb = cv.take<uint64_t>(1);
+    if (base_bits) *base_bits = bb;
+}
+
+static size_t lzw_bytes(uint32_t nb, uint32_t block)
+{
+    mi_carver cv; LzwScratch sc;
+    lzw_carve(cv, nb, block, &sc, nullptr);
+    return cv.bytes();
+}
+
+// the workspace of a batch of *nb blocks (a workspace the context already holds is reused whatever its size; a batch that
+// does not fit is halved)
+mi_status lzw_reserve(mi_ctx *ctx, uint32_t *nb, uint32_t block, LzwScratch *sc, uint64_t **base_bits)
+{
+    mi_status st;
+    while ((st = mi_ws_reserve(ctx, lzw_bytes(*nb, block))) == MI_ERR_NOMEM && *nb > 1) *nb = (*nb + 1) / 2;
+    if (st) return st;
     mi_carver cv(ctx->ws);
-    const size_t S = mi_align_up(block, 256);
-    sc->S = (uint32_t)S; sc->slot_words = LZW_SLOT_WORDS(block);
-    sc->eA = cv.take<uint64_t>(nb * S); sc->eB = cv.take<uint64_t>(nb * S);
-    sc->gid = cv.take<uint32_t>(nb * S); sc->rd = cv.take<uint32_t>(nb * S);
-    sc->cstart = cv.take<uint32_t>(nb * (S + 2)); sc->ncl = cv.take<uint32_t>((size_t)nb * 4);
-    sc->t_live = cv.take<uint8_t>(nb * (S + 64));
-    sc->t_pos = cv.take<uint32_t>(nb * S); sc->t_mix = cv.take<uint32_t>(nb * S); sc->slot_of = cv.take<uint32_t>(nb * S);
-    sc->cand = cv.take<uint32_t>(nb * S);
-    sc->ent = cv.take<uint32_t>(nb * S); sc->relw = cv.take<uint32_t>(nb * S); sc->cand_e = cv.take<uint16_t>(nb * S);
-    for (int c = 0; c < 6; ++c) sc->clist[c] = cv.take<uint64_t>(nb * S / 2 + 64);
-    sc->ccount = cv.take<uint32_t>(64);
-    sc->slot = cv.take<uint32_t>((size_t)nb * sc->slot_words);
-    sc->block_bits = cv.take<uint64_t>(nb + 1);
+    lzw_carve(cv, *nb, block, sc, base_bits);
+    return MI_OK;
 }
 
-// blocks per batch.  The workspace is ~80 bytes per input byte (lzw_scratch_bytes: S * 78 + the table bytes + the output
+// blocks per batch.  The workspace is ~80 bytes per input byte (lzw_arrays: S * 78 + the table bytes + the output
 // slot), so 256 MiB of input per batch — what keeps the latency chains of the time-sliced finder long enough to fill the
 // chip — is ~21 GiB of workspace: nothing beside 288 GB of HBM, too much for a card that is nearly full.  The batch is
 // therefore also held to half of the memory that is free right now, and the caller halves it again on MI_ERR_NOMEM.
@@ -703,7 +721,8 @@ uint32_t lzw_batch_blocks(mi_ctx *ctx, uint64_t nblocks, uint32_t block)
     uint64_t cap = (256ull << 20) / block;                                 // 256 MiB of input per batch
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const uint64_t fit = (uint64_t)(free_b / 2 + (ctx ? ctx->ws_bytes : 0)) / (lzw_scratch_bytes(1, block) - 65536);   // (the workspace it already holds is reused)
+        const size_t per_block = lzw_bytes(2, block) - lzw_bytes(1, block);                   // what one more block adds
+        const uint64_t fit = (uint64_t)(free_b / 2 + (ctx ? ctx->ws_bytes : 0)) / per_block;    // (the workspace it already holds is reused)
         if (fit < cap) cap = fit;
     } else (void)hipGetLastError();
     if (cap < 1) cap = 1;
@@ -767,10 +786,7 @@ mi_status lzw_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, u
 static LzwScratch lzw_view_at(const LzwScratch &ws, uint32_t lb)
 {
     LzwScratch v = ws;
-    const size_t S = ws.S, o = (size_t)lb * S;
-    v.eA += o; v.eB += o; v.gid += o; v.rd += o; v.cstart += (size_t)lb * (S + 2); v.ncl += (size_t)lb * 4;
-    v.t_live += (size_t)lb * (S + 64); v.t_pos += o; v.t_mix += o; v.slot_of += o; v.cand += o; v.ent += o; v.relw += o; v.cand_e += o;
-    v.slot += (size_t)lb * ws.slot_words; v.block_bits += lb;
+    lzw_arrays(v, [&](auto *&p, size_t per, size_t, bool rows) { if (rows) p += (size_t)lb * per; });
     return v;                                            // (the class lists and their counters are shared: lzw_find resets them)
 }
 
