@@ -81,7 +81,9 @@ struct Lz2BigDesc {
     uint32_t count;
     uint32_t anom;                           // slot (relative to the cluster) of bucket 0, or ~0u
     uint32_t limit;                          // slot of bucket T for deflate's non-wrapping find, or ~0u
-    uint32_t pad[3];
+    uint32_t pad[3];                         // [0]: start of the cluster's part in the block's plist; [1]: `pre` — exported as 0; k_lz2_prefix
+                                             // (classes 3, 4, 5, plain clusters) leaves here how many entries from the front it has placed and
+                                             // answered: bigrs[i] then holds the SLOT of entry i < pre, bigcand[i] its result; [2]: free
 };
 
 struct Lz2Scratch {
@@ -105,4 +107,5 @@ struct Lz2Scratch {
     uint64_t     *dbg;                               // phase cycle counters (MI_LZ_DEBUG=1), else NULL
     uint32_t      wave_min;                          // see lz2_class_of
     uint32_t      stop_phase;                        // measurement only (MI_LZ_STOP_PHASE=k): k_lz2_find leaves after phase k; 0 = run everything
+    uint32_t      prefix;                            // 1: k_lz2_prefix runs ahead of the wave / row replays (MI_LZ_PREFIX=0: off, A/B)
 };

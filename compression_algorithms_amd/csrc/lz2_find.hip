@@ -759,6 +759,98 @@ void k_lz2_find_wide(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
 }
 
 // =============================================================================================
+// The insert-only prefix of the wave-class clusters, placed in bulk.  A PLAIN cluster (not the one that covers
+// bucket 0 / T) retires nothing before the first entry whose position exceeds pos[0] + W; up to there — `pre` entries — find()
+// is the word id (or none for the word's first occurrence) and insert is pure first fit, and a maximal run of
+// consecutive entries with the same home r takes the next free slots >= r in order: no dependency from entry to entry.  One wave
+// per exported cluster of classes 3, 4 and 5 (128..1024 entries), ahead of the replays and with no LDS: the occupancy bitmap
+// (<= 1024 slots) is one register per lane as in WaveBitmap<1>; a step finds the first word with a free bit >= r (ballot), the
+// lanes that hold a free bit of it rank themselves (popcount below), and the first min(run, free bits) of them store their
+// slot for the run's entries.  A run that outlasts the word goes on in the next step.
+// Out: the SLOT of every entry i < pre IN PLACE over bigrs[i] (the home of a placed entry is dead: the replays read one array
+// for "slot below pre, home from pre on", and the workspace does not grow), bigcand[i] for i < pre, `pre` in the descriptor's
+// pad[1]; a cluster with pre == count is finished and flagged like those of k_lz2_dom / k_lz2_rows.  k_lz2_rows and
+// big_replay<.., PRE> rebuild their tables from the slots and start at entry `pre`.
+// Reference behaviour emulated: insert_hash_table / find, algorithms/lz77/lz77.c:55-108.
+// =============================================================================================
+#define LZ2_DOM_DONE 0x80000000u
+#ifdef MI_TEST_HOOKS                                       /* lib_test only: [0] clusters started from a precomputed prefix (or finished by it), [1] entries it answered */
+__device__ unsigned long long g_lz2_prefix_stats[2];
+#define LZ2_PREFIX_COUNT(who, entries) do { if (who) { atomicAdd(&g_lz2_prefix_stats[0], 1ull); atomicAdd(&g_lz2_prefix_stats[1], (unsigned long long)(entries)); } } while (0)
+#else
+#define LZ2_PREFIX_COUNT(who, entries) do { } while (0)
+#endif
+
+__global__ __launch_bounds__(64)
+void k_lz2_prefix(LzP P, Lz2Scratch sc)
+{
+    const uint32_t lane = threadIdx.x;
+    const uint32_t W = 1u << P.wbits;
+    // the long clusters first (their replays are launched first)
+    const uint32_t n4 = sc.big_count[4], n5 = sc.big_count[5], ncl = n4 + n5 + sc.big_count[3];
+    auto desc_of = [&](uint32_t c) -> Lz2BigDesc * { return c < n4 ? sc.desc[4] + c : c < n4 + n5 ? sc.desc[5] + (c - n4) : sc.desc[3] + (c - n4 - n5); };
+    // the cluster that covers bucket 0 / T keeps pre = 0 and the literal replay
+    auto ours = [](const uint4 &d, uint32_t limit) -> bool { return d.z != 0u && d.z <= LZ2_BIG_SMALL && d.w == ~0u && limit == ~0u; };
+    // (measured: with the descriptor and the first entries of a wave's next cluster prefetched while it works, the span beside
+    // k_lz2_partition stayed at 0.29 ms per launch — the steps below, not the loads, are the time; the prefetch was removed)
+    for (uint32_t ci = blockIdx.x; ci < ncl; ci += gridDim.x) {
+        Lz2BigDesc *dp = desc_of(ci);
+        const uint4 c_a = *reinterpret_cast<const uint4 *>(dp);          // block, start, count, anom
+        if (!ours(c_a, dp->limit)) continue;
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)c_a.z);
+        const size_t at = (size_t)c_a.x * LZ2_BIG_STRIDE + c_a.y;
+        const uint16_t *bp = sc.bigpos + at, *bi = sc.bigpid + at;
+        uint16_t *br = sc.bigrs + at, *bc = sc.bigcand + at;
+        uint32_t bm = 0;                                                // word `lane` of the occupancy bitmap
+        uint32_t pre = 0;
+        uint32_t n_pos = 0, n_rs = 0, n_pid = 0;
+        if (lane < n) { n_pos = bp[lane]; n_rs = br[lane]; n_pid = bi[lane]; }
+        const uint32_t last = RLANE(n_pos, 0) + W;                      // entries up to this position see no retirement
+        for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+            const uint32_t ii = i0 + lane;
+            const uint32_t c_pos = n_pos, c_rs = n_rs, c_pid = n_pid;
+            if (ii + 64 < n) { n_pos = bp[ii + 64]; n_rs = br[ii + 64]; n_pid = bi[ii + 64]; }
+            // positions ascend: the lanes inside the prefix are the lowest ones
+            const uint64_t inside = __ballot(ii < n && c_pos <= last);
+            const uint32_t lim = ~inside ? (uint32_t)__builtin_ctzll(~inside) : 64u;
+            if (lim == 0u) break;
+            if (lane < lim) bc[ii] = (uint16_t)(c_pid == c_pos ? (uint32_t)LZ_NONE16 : c_pid);
+            const uint32_t below = (uint32_t)__shfl_up((int)c_rs, 1);
+            const uint64_t heads = __ballot(lane < lim && (lane == 0u || c_rs != below));   // first entries of the runs of equal homes
+            bool stuck = false;
+            for (uint32_t t = 0; t < lim;) {
+                const uint32_t r = RLANE(c_rs, t);
+                const uint64_t rest = t + 1u < 64u ? heads >> (t + 1u) : 0ull;
+                const uint32_t run = rest ? (uint32_t)__builtin_ctzll(rest) + 1u : lim - t;
+                const uint32_t rw = r >> 5;
+                uint32_t v = bm;
+                if (lane < rw) v = 0xFFFFFFFFu; else if (lane == rw) v |= (1u << (r & 31u)) - 1u;
+                const uint64_t nz = __ballot(v != 0xFFFFFFFFu);
+                if (!nz) { stuck = true; break; }                       // (2048 slots for <= 1024 entries: never)
+                const uint32_t wl = (uint32_t)__builtin_ctzll(nz);
+                const uint32_t f = ~RLANE(v, wl);                       // the free slots of that word, from r on
+                const uint32_t fc = (uint32_t)__popc(f), m = run < fc ? run : fc;
+                // lane b stands for bit b of the word: the k-th free bit is the slot of the run's k-th entry
+                const uint32_t rank = (uint32_t)__popc(f & ((1u << (lane & 31u)) - 1u));
+                const bool mine = lane < 32u && ((f >> (lane & 31u)) & 1u) && rank < m;
+                const uint32_t taken = (uint32_t)__ballot(mine);
+                if (mine) br[i0 + t + rank] = (uint16_t)((wl << 5) + lane);
+                if (lane == wl) bm |= taken;
+                t += m;
+            }
+            if (stuck) { lz_order_violation(P); break; }
+            pre += lim;
+            if (lim < 64u) break;
+        }
+        if (lane == 0) {
+            dp->pad[1] = pre;
+            if (pre == n) dp->count = n | LZ2_DOM_DONE;                 // no replay takes it
+        }
+        LZ2_PREFIX_COUNT(lane == 0 && pre == n, pre);
+    }
+}
+
+// =============================================================================================
 // wave-per-cluster replay
 // =============================================================================================
 template <int LDS_ENTRIES, int NW>
@@ -786,6 +878,16 @@ void k_lz2_big(LzP P, Lz2Scratch sc, int large)
         // the occupancy bitmap takes one register per lane and 2048 slots: a cluster is replayed with as few as it needs (every
         // first-fit and every clear walks all of them; the wide class was replayed with four whatever its size)
         const bool plain = d_anom == ~0u && d_limit == ~0u;
+        if constexpr (NW == 1) {
+            // classes 3, 4, 5: k_lz2_prefix has placed and answered the entries below dp->pad[1] (0: it did not run, or not this cluster)
+            __shared__ uint32_t s_stage[64];
+            const uint32_t pre = dp->pad[1];
+            if (plain && pre != 0u && pre < n) {
+                LZ2_PREFIX_COUNT(lane == 0, pre);
+                big_replay<LDS_ENTRIES, 1, true, true>(s_occ, s_slot, lane, W, n, d_anom, d_limit, bp, br, bi, bc, pre, s_stage);
+                continue;
+            }
+        }
         if constexpr (NW > 1) {
             if (n <= 2048u) {
                 if (plain) big_replay<LDS_ENTRIES, 1, true>(s_occ, s_slot, lane, W, n, d_anom, d_limit, bp, br, bi, bc);
@@ -811,7 +913,6 @@ void k_lz2_big(LzP P, Lz2Scratch sc, int large)
 // cluster it finishes is flagged in its descriptor; k_lz2_big<LZ2_CAP> skips those and replays the rest (not dominated, given up,
 // or covering bucket 0 / T).  Reference behaviour emulated: algorithms/lz77/lz77.c:55-108.
 // =============================================================================================
-#define LZ2_DOM_DONE 0x80000000u
 __global__ __launch_bounds__(256)
 void k_lz2_dom(LzP P, Lz2Scratch sc)
 {
@@ -903,18 +1004,19 @@ void k_lz2_rows(LzP P, Lz2Scratch sc, int cls_a, int cls_b, int cursor_slot)
     uint32_t *occ = s_occ[g], *ent = s_ent[g], *bmw = s_bm[g];
 
     bool active = false, exhausted = false;
-    uint32_t n = 0, i0 = 0, ev = 0;
+    uint32_t n = 0, i0 = 0, ev = 0, pre = 0;                // pre: entries of the cluster that k_lz2_prefix has placed and answered
     size_t at = 0;
     uint32_t cur_a = 0, cur_b = 0, out_acc = LZ_NONE16;
     // the next cluster of this row: 0 = nothing, 1 = cursor value in flight, 2 = descriptor in flight, 3 = first entries in flight / ready
-    uint32_t pf_stage = 0, pf_ci = 0, pf_count = 0;
+    uint32_t pf_stage = 0, pf_ci = 0, pf_count = 0, pf_pre = 0;
     size_t pf_at = 0;
     // Registers that ONLY loads write (no arithmetic on them before the next boundary, no conditional assignment: either would put
     // a wait for the load right behind its issue).  Every boundary reloads all of them, from a harmless address when a row has
     // nothing to ask for: r_n* = entries i0 + RL .. of the running cluster, r_f* = first RL entries of the prefetched cluster,
-    // r_d* = its descriptor, tk = lane 0's ticket from the cursor.
+    // r_d* = its descriptor, tk = lane 0's ticket from the cursor.  With a precomputed prefix the "first" entries of a cluster are
+    // those of the pass that holds entry `pre`.
     uint32_t r_np = 0, r_ni = 0, r_nr = 0, r_fp = 0, r_fi = 0, r_fr = 0, tk = 0;
-    uint4 r_d4 = make_uint4(0, 0, 0, 0); uint32_t r_d1 = 0;
+    uint4 r_d4 = make_uint4(0, 0, 0, 0); uint32_t r_d1 = 0, r_d6 = 0;
     // a zero the compiler cannot see through: on a provably uniform address it turns the cursor's atomic into its wave-aggregated
     // form and reads the result back on the spot
     uint32_t vzero;
@@ -922,7 +1024,7 @@ void k_lz2_rows(LzP P, Lz2Scratch sc, int cls_a, int cls_b, int cursor_slot)
 
     for (;;) {
         // ================= boundary: USES (everything read here was loaded at least one pass ago) =================
-        const bool flush = active && i0 + l < n;
+        const bool flush = active && i0 + l < n && i0 + l >= pre;          // (below pre: k_lz2_prefix has written them)
         uint16_t *const flush_to = sc.bigcand + at + i0 + l;
         if (active) {
             i0 += (uint32_t)RL;
@@ -933,8 +1035,8 @@ void k_lz2_rows(LzP P, Lz2Scratch sc, int cls_a, int cls_b, int cursor_slot)
         uint32_t done_ci = 0, done_n = 0;
         if (!active && pf_stage == 3u) {
             take = true;
-            n = pf_count; at = pf_at;
-            cur_a = r_fp | (r_fi << 16); cur_b = r_fr; i0 = 0; ev = 0; active = true; pf_stage = 0;
+            n = pf_count; at = pf_at; pre = pf_pre;
+            cur_a = r_fp | (r_fi << 16); cur_b = r_fr; i0 = pre & ~(uint32_t)(RL - 1); ev = 0; active = true; pf_stage = 0;
             bmw[l] = 0;
             done_ci = pf_ci; done_n = n;
         }
@@ -944,7 +1046,7 @@ void k_lz2_rows(LzP P, Lz2Scratch sc, int cls_a, int cls_b, int cursor_slot)
         } else if (pf_stage == 2u) {
             // the cluster that covers bucket 0 / T (and anything that does not fit): not ours, another one
             if (r_d4.w != ~0u || r_d1 != ~0u || r_d4.z > (uint32_t)CAPE || r_d4.z < 2u * RL) pf_stage = 0;
-            else { pf_count = r_d4.z; pf_at = (size_t)r_d4.x * LZ2_BIG_STRIDE + r_d4.y; pf_stage = 3; }
+            else { pf_count = r_d4.z; pf_at = (size_t)r_d4.x * LZ2_BIG_STRIDE + r_d4.y; pf_pre = r_d6 < r_d4.z ? r_d6 : 0u; pf_stage = 3; }
         }
         if (pf_stage == 0u && !exhausted) { want_cursor = true; pf_stage = 1; }
         // ================= boundary: ISSUES (all unconditional loads; nothing below waits for them) =================
@@ -952,14 +1054,47 @@ void k_lz2_rows(LzP P, Lz2Scratch sc, int cls_a, int cls_b, int cursor_slot)
             const uint32_t k = i0 + (uint32_t)RL + l;
             const size_t na = (active && k < n) ? at + k : 0;
             r_np = sc.bigpos[na]; r_ni = sc.bigpid[na]; r_nr = sc.bigrs[na];
-            const size_t fa = (pf_stage == 3u) ? pf_at + l : 0;              // (>= 2 RL entries: the first RL exist)
+            const uint32_t fk = (pf_pre & ~(uint32_t)(RL - 1)) + l;           // (pre = 0: >= 2 RL entries, the first RL exist)
+            const size_t fa = (pf_stage == 3u && fk < pf_count) ? pf_at + fk : 0;
             r_fp = sc.bigpos[fa]; r_fi = sc.bigpid[fa]; r_fr = sc.bigrs[fa];
             const uint32_t *dp = reinterpret_cast<const uint32_t *>(pf_stage == 2u ? desc_of(pf_ci) : descs_a);
-            r_d4 = *reinterpret_cast<const uint4 *>(dp); r_d1 = dp[4];
+            r_d4 = *reinterpret_cast<const uint4 *>(dp); r_d1 = dp[4]; r_d6 = dp[6];
         }
         if (flush) *flush_to = (uint16_t)out_acc;
         if (take && l == 0) desc_of(done_ci)->count = done_n | LZ2_DOM_DONE;     // k_lz2_big skips it
         if (want_cursor && l == 0) tk = atomicAdd(cursor + vzero, 1u);
+        // ================= a row that starts behind a precomputed prefix: the whole wave rebuilds its table =================
+        // slot (in place of the home, k_lz2_prefix), position and word id of the entries below `pre`, 64 per iteration, the rows
+        // that take a cluster at this boundary one after the other.  ONE wait for global memory per 256 entries — at most
+        // CAPE / 256 of them per cluster start, where the replay of those entries took pre steps — and every row waits with it.
+        {
+            uint64_t starts = __ballot(take && l == 0 && pre != 0u);
+            while (starts) {
+                const uint32_t src = (uint32_t)__builtin_ctzll(starts), g2 = src / (uint32_t)RL;
+                starts &= starts - 1ull;
+                const uint32_t pre2 = RLANE(pre, src);
+                const size_t at2 = (size_t)RLANE((uint32_t)at, src) | ((size_t)RLANE((uint32_t)((uint64_t)at >> 32), src) << 32);
+                LZ2_PREFIX_COUNT(lane == 0, pre2);
+                for (uint32_t j0 = 0; j0 < pre2; j0 += 256u) {                // (the loads of four iterations in flight together)
+                    uint32_t sl[4], pp[4], idw[4];
+#pragma unroll
+                    for (uint32_t u = 0; u < 4u; ++u) {
+                        const uint32_t j = j0 + 64u * u + lane;
+                        const size_t ja = j < pre2 ? at2 + j : 0;
+                        sl[u] = sc.bigrs[ja]; pp[u] = sc.bigpos[ja]; idw[u] = sc.bigpid[ja];
+                    }
+#pragma unroll
+                    for (uint32_t u = 0; u < 4u; ++u) {
+                        const uint32_t j = j0 + 64u * u + lane;
+                        if (j < pre2 && sl[u] < (uint32_t)CAPE) {
+                            s_occ[g2][sl[u]] = idw[u] | (pp[u] << 16); s_ent[g2][j] = sl[u] | (pp[u] << 16);
+                            atomicOr(&s_bm[g2][sl[u] >> 5], 1u << (sl[u] & 31u));    // (behind the row's own bmw[l] = 0, in the LDS queue's order)
+                        }
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
         if (__ballot(active || pf_stage != 0u) == 0ull) break;
         if (__ballot(active) == 0ull) continue;
         // ================= RL steps: LDS, cross-lane and vector work only =================
@@ -970,7 +1105,7 @@ void k_lz2_rows(LzP P, Lz2Scratch sc, int cls_a, int cls_b, int cursor_slot)
         uint32_t e = ent[(active && ev + l < i0) ? ev + l : 0u];
         for (uint32_t t = 0; t < (uint32_t)RL; ++t) {
             const uint32_t i = i0 + t;
-            const bool on = active && i < n;
+            const bool on = active && i < n && i >= pre;                      // (the pass that holds entry `pre`: the ones below are off)
             const uint32_t p = a & 0xFFFFu, id = a >> 16;
             for (;;) {                                                      // FIFO retirement (lz77.c:70-76): normally one pass
                 const bool ret = on && ev + l < i && (e >> 16) + W < p;
@@ -1263,6 +1398,8 @@ void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
     sc->dbg = getenv("MI_LZ_DEBUG") ? cv.take<uint64_t>(64) : nullptr;
     // bits 16..: the row replay's switch (MI_LZ_ROWS, lz2_stage_b): with it the wave classes are three (128..255 apart)
     { const char *e = getenv("MI_LZ_ROWS"); const uint32_t rows = e ? (uint32_t)atoi(e) : 1u; sc->wave_min = LZ2_WAVE | ((rows ? 1u : 0u) << 16); }
+    // MI_LZ_PREFIX=0: no k_lz2_prefix, every replay starts at entry 0 (A/B and the parity test, nothing else)
+    { const char *e = getenv("MI_LZ_PREFIX"); sc->prefix = e ? (atoi(e) ? 1u : 0u) : 1u; }
 #ifdef MI_MEASURE
     sc->stop_phase = getenv("MI_LZ_STOP_PHASE") ? (uint32_t)atoi(getenv("MI_LZ_STOP_PHASE")) : 0u;
 #else
@@ -1285,6 +1422,21 @@ extern "C" int mi_lz_debug_counters(mi_ctx *ctx, uint64_t *out32)
     (void)hipDeviceSynchronize();
     return hipMemcpy(out32, ctx->lz_dbg, 64 * 8, hipMemcpyDeviceToHost) == hipSuccess ? 1 : 0;      // 64 counters: [0..31] find / parse, [32..47] partition
 }
+
+#ifdef MI_TEST_HOOKS
+// lib_test only (tests/test_prefix_replay_gpu.py): out2[0] = clusters whose replay started from a precomputed prefix or that the
+// prefix finished, out2[1] = entries it answered, since the last reset; reset != 0 zeroes both afterwards.  0 on a HIP error.
+extern "C" int mi_test_prefix_stats(mi_ctx *ctx, uint64_t *out2, int reset)
+{
+    if (!ctx || !out2) return 0;
+    unsigned long long h[2] = {0, 0};
+    if (hipDeviceSynchronize() != hipSuccess) return 0;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_lz2_prefix_stats), sizeof h) != hipSuccess) return 0;
+    out2[0] = h[0]; out2[1] = h[1];
+    if (reset) { h[0] = h[1] = 0; if (hipMemcpyToSymbol(HIP_SYMBOL(g_lz2_prefix_stats), h, sizeof h) != hipSuccess) return 0; }
+    return 1;
+}
+#endif
 
 // stage A1: partition (also decides which blocks go to the fallback pipeline)
 mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
@@ -1370,6 +1522,10 @@ mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &
           hipLaunchKernelGGL(k_lz2_lanes, dim3((uint32_t)waves), dim3(64), budget_dw * 4u, s, P, sc, LANE_SIZES - 1u, LZ2_BIG, budget_dw); }
     }
     if (which & 2) {
+    // the insert-only prefix of every plain wave-class cluster first (no LDS, a striding grid): the replays below start behind it
+    if (sc.prefix) { mi_prof_scope p(ctx, "k_lz2_prefix", s, (uint64_t)nb * P.block);
+      const uint64_t worst = (uint64_t)nb * (lz2_class_cap(3) + lz2_class_cap(4) + lz2_class_cap(5));
+      hipLaunchKernelGGL(k_lz2_prefix, dim3((unsigned)(worst < (uint64_t)ncu * 32u ? worst : (uint64_t)ncu * 32u)), dim3(64), 0, s, P, sc); }
     { mi_prof_scope p(ctx, "k_lz2_big", s, (uint64_t)nb * P.block);
       // the 512..1024-entry class first and alone on the wave replay (6 KiB of LDS per wave), then the 128..511-entry clusters: on the
       // row replay (below), or — MI_LZ_ROWS=0 — on the wave replay with 3 KiB per wave (MI_LZ_BIG_SPLIT=0: one launch for both wave

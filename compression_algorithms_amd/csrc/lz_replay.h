@@ -117,11 +117,16 @@ struct WaveBitmap {
 
 // one cluster, one wave.  PLAIN: the cluster does not cover bucket 0 / T (all but one per block): the spurious clear and
 // the non-wrapping find() drop out of the loop, which is bound by the number of scalar instructions per step.
-template <int LDS_ENTRIES, int NW, bool PLAIN>
+// PRE (PLAIN, one bitmap register): k_lz2_prefix (lz2_find.hip) has answered and placed the entries below `pre` (> 0, < n) —
+// the insert-only prefix, nothing retired before entry `pre`: br[i] holds the SLOT of entry i < pre, not its home.  The
+// table is rebuilt from those slots 64 entries at a time (the bitmap's bits through s_stage, 64 dwords of LDS) and the
+// loop starts at entry `pre`; the first-occurrence shortcut (ev == 0) cannot be met from there on and is not compiled.
+template <int LDS_ENTRIES, int NW, bool PLAIN, bool PRE = false>
 __device__ __forceinline__ void big_replay(uint32_t *s_occ, uint16_t *s_slot, uint32_t lane, uint32_t W, uint32_t n,
                                            uint32_t d_anom, uint32_t d_limit, const uint16_t *bp, const uint16_t *br,
-                                           const uint16_t *bi, uint16_t *bc)
+                                           const uint16_t *bi, uint16_t *bc, uint32_t pre = 0, uint32_t *s_stage = nullptr)
 {
+    static_assert(!PRE || (PLAIN && NW == 1), "a precomputed prefix: plain clusters of the one-register classes only");
     WaveBitmap<NW> bm;
     bm.clear();
     uint32_t ev = 0;
@@ -131,13 +136,37 @@ __device__ __forceinline__ void big_replay(uint32_t *s_occ, uint16_t *s_slot, ui
     uint32_t ev_pos = lane < n ? bp[lane] : 0u;
     uint32_t pe = RLANE(ev_pos, 0);
     uint32_t n_pos = ev_pos, n_rs = 0, n_pid = 0;                   // the next 64 entries are in flight while these are replayed
-    if (lane < n) { n_rs = br[lane]; n_pid = bi[lane]; }
-    for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+    uint32_t i_first = 0;
+    if constexpr (PRE) {
+        i_first = pre & ~63u;                                       // the group of 64 that holds entry `pre`
+        const uint32_t q = i_first + lane;
+        n_pos = 0;
+        if (q < n) { n_pos = bp[q]; n_rs = br[q]; n_pid = bi[q]; }
+        s_stage[lane] = 0;
+        for (uint32_t j0 = 0; j0 < pre; j0 += 256) {                // (the loads of four iterations in flight together)
+            uint32_t sl[4] = {0, 0, 0, 0}, pp[4] = {0, 0, 0, 0}, idw[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) { const uint32_t j = j0 + 64u * u + lane; if (j < pre) { sl[u] = br[j]; pp[u] = bp[j]; idw[u] = bi[j]; } }
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                const uint32_t j = j0 + 64u * u + lane;
+                if (j < pre) {
+                    if (sl[u] < (uint32_t)LDS_ENTRIES) { s_occ[sl[u]] = idw[u] | (pp[u] << 16); atomicOr(&s_stage[sl[u] >> 5], 1u << (sl[u] & 31u)); }
+                    s_slot[j] = (uint16_t)sl[u];
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        bm.w[0] = s_stage[lane];
+    } else if (lane < n) { n_rs = br[lane]; n_pid = bi[lane]; }
+    for (uint32_t i0 = i_first; i0 < n; i0 += 64) {
         const uint32_t ii = i0 + lane;
         c_pos = n_pos; c_rs = n_rs; c_pid = n_pid;
         if (ii + 64 < n) { n_pos = bp[ii + 64]; n_rs = br[ii + 64]; n_pid = bi[ii + 64]; }
         const uint32_t lim = (n - i0) < 64u ? (n - i0) : 64u;
-        for (uint32_t t = 0; t < lim; ++t) {
+        uint32_t t_first = 0;
+        if constexpr (PRE) t_first = pre > i0 ? pre - i0 : 0u;      // (the first group only)
+        for (uint32_t t = t_first; t < lim; ++t) {
             const uint32_t i = i0 + t;
             const uint32_t p = RLANE(c_pos, t), r = RLANE(c_rs, t), id = RLANE(c_pid, t);
             while (ev < i && pe + W < p) {                          // FIFO retirement (lz77.c:70-76)
@@ -149,7 +178,7 @@ __device__ __forceinline__ void big_replay(uint32_t *s_occ, uint16_t *s_slot, ui
             }
             if (!PLAIN && anom_pending && p > W - 1u) { bm.clear_bit(d_anom, lane); anom_pending = false; }
             uint32_t res = LZ_NONE16;
-            if (PLAIN && ev == 0) {
+            if (!PRE && PLAIN && ev == 0) {
                 // nothing evicted yet: find() = the word's first occurrence = the word id (k_lz2_find, the sweep)
                 if (id != p) res = id;
             } else if (id != p) {                                       // (the first occurrence of a word in the block finds nothing, ever)
@@ -181,7 +210,7 @@ __device__ __forceinline__ void big_replay(uint32_t *s_occ, uint16_t *s_slot, ui
             if (lane == t) out_acc = res;
             __builtin_amdgcn_wave_barrier();
         }
-        if (ii < n) bc[ii] = (uint16_t)out_acc;
+        if (ii < n && (!PRE || ii >= pre)) bc[ii] = (uint16_t)out_acc;     // (below `pre`: k_lz2_prefix has written them)
     }
     __builtin_amdgcn_wave_barrier();
 }
