@@ -21,12 +21,24 @@
 // "return at once": the stages behind the six kernels (find, replay, the fallback chain) index per-block records that an early
 // exit would leave as the previous batch wrote them; a one-byte block is a case every stage already handles.  A tight bound
 // (mi_deflate_batch_max_blocks of the exact total) has fewer than total / block + 1 of them.
+//
+// A preset dictionary (mi_deflate_batch_dict_dev; zlib's deflateSetDictionary): one per call, read-only.  U, its last
+// min(dict_bytes, 32 768, block / 2) bytes, lies in front of every item's first block, which holds block - |U| bytes of the item
+// so that U and the head are one block to the finder (internal.h: dfb_first, dfb_nblk); the later blocks are today's.
+//   k_dfb_stage    per pipeline batch, one workgroup per block: for an item's first block, U and the item's head into the block
+//                  slot's CELL of the batch's scratch set — the finder wants contiguous bytes.  The descriptor points at the cell
+//                  with n = |U| + head and skip = |U|; the parse starts at skip (k_lz_parse_emit<DESC, DICT>), the entropy stage
+//                  and the checksums work on the item's bytes behind it.  Cells: one block-sized cell per block slot of a set,
+//                  whatever the count of items.
+//   the zlib header is then 78 BB and the Adler-32 of the WHOLE dictionary (DICTID), computed on the stream
 #include "lz_common.h"
 #include "crc32.h"
 #include "adler32.h"
 #include "internal.h"
 
-#define DFB_HEAD      256u                     // workspace head: u32 nreal, u64 carry[2] at byte 8, a zero byte at byte 64 (the PAD block)
+#define DFB_HEAD      256u                     // workspace head: u32 nreal, u64 carry[2] at byte 8, a zero byte at byte 64 (the PAD block),
+                                               // u32 DICTID at byte 128
+#define DFB_DICTID_AT 128u
 
 struct DfbWs {
     uint8_t   *head;
@@ -35,6 +47,7 @@ struct DfbWs {
     uint64_t  *item_total;                     // [count] bytes of the item's records (written with its last block)
     uint32_t  *ck;                             // [2 * max_blocks] per block: pure CRC-32, or the raw Adler sums a, s
     LzBlkDesc *desc;                           // [max_blocks]
+    uint8_t   *zck;                            // the partials of the dictionary's Adler-32 (zlib with a dictionary)
     size_t     bytes;
 };
 
@@ -48,11 +61,18 @@ static DfbWs dfb_carve(void *ws, const DfbCall &b)
     w.item_total = cv.take<uint64_t>(b.count);
     w.ck = cv.take<uint32_t>(2 * b.max_blocks);
     w.desc = cv.take<LzBlkDesc>(b.max_blocks);
+    w.zck = b.ulen && b.container == MI_CONTAINER_ZLIB ? cv.take<uint8_t>(defz_ws_bytes()) : nullptr;
     w.bytes = cv.bytes();
     return w;
 }
 
 size_t dfb_ws_bytes(const DfbCall &b) { return dfb_carve(nullptr, b).bytes; }
+
+// one cell per block slot of a scratch set, and room for the 16-byte words the block loaders round their reads out to
+size_t dfb_stage_bytes(const DfbCall &b, uint32_t nbmax, uint32_t block) { return b.ulen ? (size_t)nbmax * block + 64u : 0; }
+
+// the container header's bytes: with a dictionary the zlib header carries DICTID
+static uint32_t dfb_header_bytes(const DfbCall &b) { return defz_header_bytes(b.container) + (b.ulen && b.container == MI_CONTAINER_ZLIB ? 4u : 0u); }
 
 struct OpAddU64 { __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; } };
 
@@ -72,7 +92,7 @@ void k_dfb_scan(DfbCall b, uint32_t block, uint32_t *__restrict__ item_first, ui
         if (i < count) {
             const uint64_t nb = b.in_bytes[i], cap = b.out_cap[i];
             if ((nb && !b.in[i]) || (cap && !b.out[i]) || nb > DFB_MAX_BYTES || cap > DFB_MAX_BYTES) st = MI_ERR_ARG;
-            else nblk = (nb + block - 1u) / block;
+            else nblk = dfb_nblk(nb, block, b.ulen);
         }
         uint64_t tot;
         const uint64_t first = run + block_exclusive_scan<uint64_t>(nblk, OpAddU64(), 0ull, s_tmp, &tot);
@@ -98,6 +118,7 @@ void k_dfb_fill(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_fir
     if (g64 >= b.max_blocks) return;
     const uint32_t g = (uint32_t)g64;
     LzBlkDesc d;
+    d.skip = 0;
     if (g >= *nreal) { d.src = pad_byte; d.n = 1u; d.item = LZ_DESC_PAD; d.blk = 0u; d.last = 0u; }
     else {
         // the last item whose first block is <= g: items without blocks share their first block with the next item that has
@@ -105,22 +126,40 @@ void k_dfb_fill(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_fir
         uint32_t lo = 0, hi = (uint32_t)b.count - 1u;
         while (lo < hi) { const uint32_t mid = lo + (hi - lo + 1u) / 2u; if (item_first[mid] <= g) lo = mid; else hi = mid - 1u; }
         const uint32_t blk = g - item_first[lo];
-        const uint64_t nb = b.in_bytes[lo], off = (uint64_t)blk * block;
+        const uint64_t nb = b.in_bytes[lo], off = dfb_begin_of(blk, block, b.ulen), room = blk ? block : block - b.ulen;
         d.src = reinterpret_cast<const uint8_t *>(b.in[lo]) + off;
-        d.n = (uint32_t)((nb - off) < block ? (nb - off) : block);
-        d.item = lo; d.blk = blk; d.last = off + block >= nb ? 1u : 0u;
+        d.n = (uint32_t)((nb - off) < room ? (nb - off) : room);
+        d.item = lo; d.blk = blk; d.last = off + room >= nb ? 1u : 0u;
+        if (b.ulen && blk == 0u) {
+            // the item's first block is read from its cell, behind U (k_dfb_stage fills it when the block's pipeline batch comes up)
+            d.src = b.stage[(g / b.nbmax) % b.nsets] + (size_t)(g % b.nbmax) * block;
+            d.n += b.ulen; d.skip = (uint16_t)b.ulen;
+        }
     }
     desc[g] = d;
 }
 
+// the cells of one pipeline batch: U, then the head of the item whose first block this is
+__global__ __launch_bounds__(256)
+void k_dfb_stage(DfbCall b, const LzBlkDesc *__restrict__ desc, uint64_t b0)
+{
+    const LzBlkDesc d = desc[b0 + blockIdx.x];
+    if (d.item == LZ_DESC_PAD || d.skip == 0u) return;                 // (the whole workgroup)
+    uint8_t *cell = const_cast<uint8_t *>(d.src);                      // (inside this set's staging area: k_dfb_fill placed it)
+    const uint8_t *u = b.dict + (b.dict_bytes - d.skip), *head = reinterpret_cast<const uint8_t *>(b.in[d.item]);
+    for (uint32_t i = threadIdx.x; i < d.n; i += 256u) cell[i] = i < d.skip ? u[i] : head[i - d.skip];
+}
+
+// (a staged block's own bytes are read where the item has them: its cell is not filled before its pipeline batch comes up)
 template <bool CRC>
 __global__ __launch_bounds__(ZCK_THREADS)
-void k_dfb_cksum(const LzBlkDesc *__restrict__ desc, uint32_t *__restrict__ ck)
+void k_dfb_cksum(const LzBlkDesc *__restrict__ desc, uint32_t *__restrict__ ck, const void *const *__restrict__ in)
 {
     __shared__ typename std::conditional<CRC, CrcLds, AdlerLds>::type s_lds;
     const uint32_t tid = threadIdx.x, g = blockIdx.x;
-    const LzBlkDesc d = desc[g];
+    LzBlkDesc d = desc[g];
     if (d.item == LZ_DESC_PAD) return;                                 // (the whole workgroup)
+    if (d.skip) { d.src = reinterpret_cast<const uint8_t *>(in[d.item]); d.n -= d.skip; }
     if constexpr (CRC) {
         crc_lds_init(s_lds, tid);
         __syncthreads();
@@ -189,7 +228,7 @@ __constant__ uint8_t kDfbGzip[10] = {0x1F, 0x8B, 0x08, 0x00, 0x00, 0x00, 0x00, 0
 
 __global__ __launch_bounds__(64)
 void k_dfb_finish(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_first, const uint32_t *__restrict__ item_st,
-                  const uint64_t *__restrict__ item_total, const uint32_t *__restrict__ ck)
+                  const uint64_t *__restrict__ item_total, const uint32_t *__restrict__ ck, const uint32_t *__restrict__ dictid)
 {
     const uint32_t lane = threadIdx.x, i = blockIdx.x;
     const uint32_t st0 = item_st[i];
@@ -198,13 +237,14 @@ void k_dfb_finish(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_f
         return;
     }
     const uint64_t nb = b.in_bytes[i];
-    const uint32_t nblk = (uint32_t)((nb + block - 1u) / block), first = item_first[i];
+    const uint32_t nblk = (uint32_t)dfb_nblk(nb, block, b.ulen), first = item_first[i];
+    auto end_of = [&](uint32_t k) -> uint64_t { const uint64_t e = dfb_begin_of(k + 1u, block, b.ulen); return e < nb ? e : nb; };
     // ---- the item's checksum from its blocks' parts: a part moves to the end of the item by the bytes behind its block
     uint32_t check = 0;
     if (b.container == MI_CONTAINER_GZIP) {
         uint32_t c = 0;
         for (uint32_t k = lane; k < nblk; k += 64u) {
-            const uint64_t end = (uint64_t)(k + 1u) * block < nb ? (uint64_t)(k + 1u) * block : nb;
+            const uint64_t end = end_of(k);
             c ^= crc_mulmod(ck[2u * (first + k)], crc_xpow8(nb - end));
         }
         for (int o = 32; o > 0; o >>= 1) c ^= __shfl_xor(c, o);
@@ -212,7 +252,7 @@ void k_dfb_finish(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_f
     } else if (b.container == MI_CONTAINER_ZLIB) {
         uint64_t A = 0, S = 0;
         for (uint32_t k = lane; k < nblk; k += 64u) {
-            const uint64_t end = (uint64_t)(k + 1u) * block < nb ? (uint64_t)(k + 1u) * block : nb;
+            const uint64_t end = end_of(k);
             const uint64_t a = ck[2u * (first + k)], s = ck[2u * (first + k) + 1u];
             A += a;
             S += (s + a * ((nb - end) % ADLER_MOD)) % ADLER_MOD;
@@ -225,7 +265,11 @@ void k_dfb_finish(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_f
     const uint64_t cap = b.out_cap[i];
     auto put = [&](uint64_t at, uint32_t v) { if (at < cap) out[at] = (uint8_t)v; };
     uint64_t r = 0;
-    if (b.container == MI_CONTAINER_ZLIB) { put(0, 0x78); put(1, 0x9C); r = 2; }
+    if (b.container == MI_CONTAINER_ZLIB && b.ulen) {                 // FDICT, and DICTID: the Adler-32 of the whole dictionary
+        const uint32_t id = *dictid;
+        put(0, 0x78); put(1, 0xBB); r = 2;
+        for (int k = 0; k < 4; ++k) put(r++, id >> (24 - 8 * k));
+    } else if (b.container == MI_CONTAINER_ZLIB) { put(0, 0x78); put(1, 0x9C); r = 2; }
     else if (b.container == MI_CONTAINER_GZIP) { for (uint32_t k = 0; k < 10u; ++k) put(k, kDfbGzip[k]); r = 10; }
     r += nblk ? item_total[i] : 0ull;
     put(r++, 0x03); put(r++, 0x00);                                    // BFINAL = 1, fixed, end-of-block; padding
@@ -248,13 +292,17 @@ mi_status dfb_begin(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hip
     MI_HIP(ctx, hipMemsetAsync(w.head, 0, DFB_HEAD, s));
     if (b.failed) MI_HIP(ctx, hipMemsetAsync(b.failed, 0, 4, s));
     uint32_t *nreal = reinterpret_cast<uint32_t *>(w.head);
+    if (w.zck) {                                                        // DICTID, on the stream: k_dfb_finish writes it into every header
+        const mi_status st = defz_checksum(ctx, false, b.dict, b.dict_bytes, w.zck, reinterpret_cast<uint32_t *>(w.head + DFB_DICTID_AT), s);
+        if (st) return st;
+    }
     mi_prof_scope pr(ctx, "k_dfb_table", s, 0);
     hipLaunchKernelGGL(k_dfb_scan, dim3(1), dim3(1024), 0, s, b, block, w.item_first, w.item_st, nreal);
     if (b.max_blocks) {
         hipLaunchKernelGGL(k_dfb_fill, dim3((unsigned)((b.max_blocks + 255u) / 256u)), dim3(256), 0, s, b, block, w.item_first, nreal,
                            w.head + 64, w.desc);
-        if (b.container == MI_CONTAINER_GZIP) hipLaunchKernelGGL(k_dfb_cksum<true>, dim3((unsigned)b.max_blocks), dim3(ZCK_THREADS), 0, s, w.desc, w.ck);
-        else if (b.container == MI_CONTAINER_ZLIB) hipLaunchKernelGGL(k_dfb_cksum<false>, dim3((unsigned)b.max_blocks), dim3(ZCK_THREADS), 0, s, w.desc, w.ck);
+        if (b.container == MI_CONTAINER_GZIP) hipLaunchKernelGGL(k_dfb_cksum<true>, dim3((unsigned)b.max_blocks), dim3(ZCK_THREADS), 0, s, w.desc, w.ck, b.in);
+        else if (b.container == MI_CONTAINER_ZLIB) hipLaunchKernelGGL(k_dfb_cksum<false>, dim3((unsigned)b.max_blocks), dim3(ZCK_THREADS), 0, s, w.desc, w.ck, b.in);
     }
     MI_HIP(ctx, hipGetLastError());
     *desc = reinterpret_cast<const uint8_t *>(w.desc);
@@ -266,14 +314,21 @@ void dfb_launch_place(const DfbCall &b, void *ws, const uint32_t *slots, const u
 {
     const DfbWs w = dfb_carve(ws, b);
     hipLaunchKernelGGL(k_dfb_place, dim3(nb), dim3(256), 0, s, b, w.desc, w.item_first, w.item_total,
-                       reinterpret_cast<uint64_t *>(w.head + 8), (uint32_t)(seq & 1u), defz_header_bytes(b.container), slots, block_bits, b0, nb);
+                       reinterpret_cast<uint64_t *>(w.head + 8), (uint32_t)(seq & 1u), dfb_header_bytes(b), slots, block_bits, b0, nb);
+}
+
+void dfb_launch_stage(const DfbCall &b, uint32_t block, void *ws, uint64_t b0, uint32_t nb, hipStream_t s)
+{
+    const DfbWs w = dfb_carve(ws, b);
+    hipLaunchKernelGGL(k_dfb_stage, dim3(nb), dim3(256), 0, s, b, w.desc, b0);
 }
 
 mi_status dfb_end(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s)
 {
     const DfbWs w = dfb_carve(ws, b);
     mi_prof_scope pr(ctx, "k_dfb_finish", s, 0);
-    hipLaunchKernelGGL(k_dfb_finish, dim3((unsigned)b.count), dim3(64), 0, s, b, block, w.item_first, w.item_st, w.item_total, w.ck);
+    hipLaunchKernelGGL(k_dfb_finish, dim3((unsigned)b.count), dim3(64), 0, s, b, block, w.item_first, w.item_st, w.item_total, w.ck,
+                       reinterpret_cast<const uint32_t *>(w.head + DFB_DICTID_AT));
     MI_HIP(ctx, hipGetLastError());
     return MI_OK;
 }
@@ -287,6 +342,48 @@ extern "C" uint64_t mi_deflate_batch_max_blocks(uint64_t total_in_bytes, uint64_
 {
     const uint64_t block = (p && p->block) ? p->block : LZ_MAX_BLOCK;
     return total_in_bytes / block + count;                             // sum of ceil(n_i / block) <= floor(sum n_i / block) + count
+}
+
+// with a dictionary of dict_bytes: the first block of an item is shorter by |U|, so an item has at most one block more, and its
+// zlib header four bytes more
+uint32_t dfb_ulen(uint64_t dict_bytes, uint32_t block)
+{
+    const uint64_t u = dict_bytes < 32768u ? dict_bytes : 32768u;
+    return (uint32_t)(u < block / 2u ? u : block / 2u);
+}
+
+extern "C" uint64_t mi_deflate_batch_dict_bound_bytes(uint64_t n_item, const mi_lz_params *p, uint32_t container, uint64_t dict_bytes)
+{
+    const uint32_t block = (p && p->block) ? p->block : LZ_MAX_BLOCK, ulen = dfb_ulen(dict_bytes, block);
+    if (!ulen) return mi_deflate_z_bound_bytes(n_item, p, container);
+    // the first block's record at its stored bound, the rest as one stream of whole blocks (which counts container and 03 00)
+    const uint64_t h = dfb_first(n_item, block, ulen);
+    return (h ? h + 5u * ((h + 65534u) / 65535u) + 5u : 0u) + mi_deflate_z_bound_bytes(n_item - h, p, container) +
+           (container == MI_CONTAINER_ZLIB ? 4u : 0u);
+}
+
+extern "C" uint64_t mi_deflate_batch_dict_max_blocks(uint64_t total_in_bytes, uint64_t count, const mi_lz_params *p, uint64_t dict_bytes)
+{
+    const uint32_t block = (p && p->block) ? p->block : LZ_MAX_BLOCK;
+    return total_in_bytes / block + (dfb_ulen(dict_bytes, block) ? 2u : 1u) * count;
+}
+
+extern "C" mi_status mi_deflate_batch_dict_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
+                                               const void *const *d_in, const uint64_t *d_in_bytes, uint64_t max_blocks,
+                                               void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                                               uint32_t *d_status, uint32_t *d_failed, const uint8_t *d_dict, uint64_t dict_bytes, void *stream)
+{
+    if (!ctx) return MI_ERR_ARG;
+    mi_status st = defz_check(p, container);
+    if (st) return st;
+    if (dict_bytes && (!d_dict || container == MI_CONTAINER_GZIP || dict_bytes > DFB_MAX_BYTES)) return MI_ERR_ARG;     // gzip has no FDICT
+    if (count > DFB_MAX_BYTES || max_blocks > DFB_MAX_BYTES) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!d_in || !d_in_bytes || !d_out || !d_out_cap || !d_out_bytes || !d_status) return MI_ERR_ARG;
+    DfbCall b{container, count, max_blocks, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, d_failed};
+    b.ulen = dfb_ulen(dict_bytes, p->block);
+    if (b.ulen) { b.dict = d_dict; b.dict_bytes = dict_bytes; }
+    return lz_encode_impl(ctx, p, nullptr, 0, nullptr, 0, nullptr, stream, LzCall{LZ_BATCH, container, nullptr, &b});
 }
 
 extern "C" mi_status mi_deflate_batch_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,

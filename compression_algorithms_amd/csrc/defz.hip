@@ -154,8 +154,9 @@ __device__ void z_canonical(const uint8_t *len, int nsym, uint32_t *tab, uint32_
     });
 }
 
-// (the body of k_defz_plan; DESC: `in` is the batched encoder's descriptor table — lz_block_src)
-template <bool DESC>
+// (the body of k_defz_plan; DESC: `in` is the batched encoder's descriptor table — lz_block_src; DICT: a block's first `skip` bytes
+// (LzBlkDesc) are a preset dictionary's tail — the record is that of the item's bytes behind them, which is what the tokens cover)
+template <bool DESC, bool DICT = false>
 __device__ __forceinline__ void defz_plan_block(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, const uint64_t *__restrict__ block_bits,
                                                 const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
 {
@@ -173,6 +174,7 @@ __device__ __forceinline__ void defz_plan_block(const uint32_t *__restrict__ tre
     uint32_t n = (uint32_t)((n_total - off) < block ? (n_total - off) : block);
     const uint8_t *src = nullptr;
     if constexpr (DESC) lz_block_src<true>(in, n_total, block, block0, lb, src, n);      // (a descriptor's block)
+    if constexpr (DICT) { const uint32_t skip = lz_block_skip<true>(in, block0, lb); src += skip; n -= skip; }
     const uint32_t ntok = (uint32_t)block_bits[lb];                    // k_lz_parse_emit left the token count here (>= 1)
     const uint32_t *trec = trec_all + (size_t)lb * LZ_MAX_BLOCK;
     uint32_t *out = slots + (size_t)lb * LZ_SLOT_WORDS;
@@ -309,6 +311,12 @@ void k_defz_plan_desc(const uint32_t *__restrict__ trec_all, uint32_t *__restric
 {
     defz_plan_block<true>(trec_all, slots, block_bits, in, n_total, block, block0);
 }
+__global__ __launch_bounds__(64)
+void k_defz_plan_dict(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, const uint64_t *__restrict__ block_bits,
+                      const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
+{
+    defz_plan_block<true, true>(trec_all, slots, block_bits, in, n_total, block, block0);
+}
 
 // byte i of the stored form of a block of n bytes (n >= 1): pieces of <= 65 535 bytes, each 00 LEN NLEN data, then the sync
 // flush 00 00 00 FF FF, then zeros
@@ -328,7 +336,7 @@ __device__ __forceinline__ uint32_t z_stored_byte(const uint8_t *src, uint32_t n
     }
 }
 
-template <bool DESC>
+template <bool DESC, bool DICT = false>
 __global__ __launch_bounds__(DEFZ_THREADS)
 void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__ slots, uint64_t *__restrict__ block_bits,
                    const uint8_t *__restrict__ in, uint64_t n_total, uint32_t block, uint64_t block0)
@@ -340,6 +348,7 @@ void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
     const uint32_t lb = blockIdx.x;
     const uint8_t *src; uint32_t n;
     lz_block_src<DESC>(in, n_total, block, block0, lb, src, n);
+    if constexpr (DICT) { const uint32_t skip = lz_block_skip<true>(in, block0, lb); src += skip; n -= skip; }   // the item's bytes
     uint32_t *out = slots + (size_t)lb * LZ_SLOT_WORDS;
     const uint32_t type = out[DEFZ_TYPE];
     if (type == 0u) {
@@ -417,8 +426,13 @@ void k_defz_encode(const uint32_t *__restrict__ trec_all, uint32_t *__restrict__
 }
 
 void defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
-                        uint32_t block, uint64_t b0, uint32_t nb, bool desc, hipStream_t s)
+                        uint32_t block, uint64_t b0, uint32_t nb, bool desc, hipStream_t s, bool dict)
 {
+    if (dict) {
+        hipLaunchKernelGGL(k_defz_plan_dict, dim3(nb), dim3(64), 0, s, trec, slots, block_bits, d_in, n, block, b0);
+        hipLaunchKernelGGL((k_defz_encode<true, true>), dim3(nb), dim3(DEFZ_THREADS), 0, s, trec, slots, block_bits, d_in, n, block, b0);
+        return;
+    }
     if (desc) {
         hipLaunchKernelGGL(k_defz_plan_desc, dim3(nb), dim3(64), 0, s, trec, slots, block_bits, d_in, n, block, b0);
         hipLaunchKernelGGL(k_defz_encode<true>, dim3(nb), dim3(DEFZ_THREADS), 0, s, trec, slots, block_bits, d_in, n, block, b0);

@@ -672,6 +672,29 @@ extern "C" mi_status mi_inflate_batch(mi_ctx *ctx, uint32_t container, uint64_t 
                          : mi_inflate_batch_size_dev(ctx, container, count, d_in, d_in_bytes, d_out_bytes, d_status, nullptr, flags, s); });
 }
 
+// ... with one preset dictionary for the call, copied up in front of the items
+extern "C" mi_status mi_inflate_batch_dict(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *h_in,
+                                           const uint64_t *h_in_bytes, void *const *h_out, const uint64_t *h_out_cap,
+                                           uint64_t *h_out_bytes, uint32_t *h_status, const uint8_t *h_dict, uint64_t dict_bytes,
+                                           uint32_t flags)
+{
+    if (!ctx || container > MI_CONTAINER_GZIP || (flags & ~MI_INFLATE_NO_CHECKSUM) || count > 0x7FFFFFFFull) return MI_ERR_ARG;
+    if (dict_bytes && (!h_dict || container == MI_CONTAINER_GZIP || dict_bytes > INFB_MAX_BYTES)) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_in || !h_in_bytes || !h_out_bytes || !h_status) return MI_ERR_ARG;
+    DevBuf dict;
+    if (!dict.alloc(dict_bytes + 16)) return MI_ERR_NOMEM;
+    if (dict_bytes) MI_HIP(ctx, hipMemcpyAsync(dict.p, h_dict, dict_bytes, hipMemcpyHostToDevice, mi_host_stream(ctx)));
+    const BatchItems b{count, h_in, h_in_bytes, h_out, h_out_cap, INFB_MAX_BYTES};
+    return batch_host_once(ctx, b, h_out_bytes, h_status,
+        [&](const void *const *d_in, const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+            uint32_t *d_status, hipStream_t s) {
+            return d_out ? mi_inflate_batch_dict_dev(ctx, container, count, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, nullptr,
+                                                     dict.as<uint8_t>(), dict_bytes, flags, s)
+                         : mi_inflate_batch_dict_size_dev(ctx, container, count, d_in, d_in_bytes, d_out_bytes, d_status, nullptr,
+                                                          dict.as<uint8_t>(), dict_bytes, flags, s); });
+}
+
 extern "C" mi_status mi_deflate_batch(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
                                       const void *const *h_in, const uint64_t *h_in_bytes,
                                       void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status)
@@ -692,6 +715,37 @@ extern "C" mi_status mi_deflate_batch(mi_ctx *ctx, const mi_lz_params *p, uint32
             [&](const void *const *d_in, const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
                 uint32_t *d_status, hipStream_t s) {
                 return mi_deflate_batch_dev(ctx, p, container, count, d_in, d_in_bytes, max_blocks, d_out, d_out_cap, d_out_bytes, d_status, nullptr, s); });
+    });
+}
+
+// ... with one preset dictionary for the call, copied up in front of the items
+extern "C" mi_status mi_deflate_batch_dict(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
+                                           const void *const *h_in, const uint64_t *h_in_bytes, void *const *h_out,
+                                           const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status, const uint8_t *h_dict,
+                                           uint64_t dict_bytes)
+{
+    if (!ctx) return MI_ERR_ARG;
+    mi_status st = defz_check(p, container);
+    if (st) return st;
+    if (dict_bytes && (!h_dict || container == MI_CONTAINER_GZIP || dict_bytes > DFB_MAX_BYTES)) return MI_ERR_ARG;
+    if (count > DFB_MAX_BYTES) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_in || !h_in_bytes || !h_out || !h_out_cap || !h_out_bytes || !h_status) return MI_ERR_ARG;
+    DevBuf dict;
+    if (!dict.alloc(dict_bytes + 16)) return MI_ERR_NOMEM;
+    if (dict_bytes) MI_HIP(ctx, hipMemcpyAsync(dict.p, h_dict, dict_bytes, hipMemcpyHostToDevice, mi_host_stream(ctx)));
+    const uint32_t ulen = dfb_ulen(dict_bytes, p->block);
+    const BatchItems b{count, h_in, h_in_bytes, h_out, h_out_cap, DFB_MAX_BYTES};
+    return host_encode_with_retry(ctx, [&]() -> mi_status {
+        uint64_t max_blocks = 0;                                           // the launch bound: the blocks of the items that go up
+        for (uint64_t i = 0; i < count; ++i)
+            if (b.in_ok(i)) max_blocks += dfb_nblk(h_in_bytes[i], p->block, ulen);
+        if (max_blocks > DFB_MAX_BYTES) return MI_ERR_ARG;
+        return batch_host_once(ctx, b, h_out_bytes, h_status,
+            [&](const void *const *d_in, const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                uint32_t *d_status, hipStream_t s) {
+                return mi_deflate_batch_dict_dev(ctx, p, container, count, d_in, d_in_bytes, max_blocks, d_out, d_out_cap, d_out_bytes, d_status,
+                                                 nullptr, dict.as<uint8_t>(), dict_bytes, s); });
     });
 }
 

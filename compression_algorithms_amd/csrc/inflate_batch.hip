@@ -13,6 +13,13 @@
 //   k_inflate_batch_check   one workgroup per item that came out MI_OK: CRC-32 (crc32.h) or Adler-32 (adler32.h) of the
 //                     decoded bytes against the item's trailer
 //
+//   DICT (mi_inflate_batch_dict_*)   one preset dictionary for the call, zlib's FDICT: its last min(dict_bytes, 32 768) bytes E
+//                     lie in front of every item that uses it (raw: every item; zlib: an item whose header has FDICT and whose
+//                     DICTID is the Adler-32 of the whole dictionary, computed on the stream by the kernels of mi_adler32_dev).
+//                     The wave preloads the last min(RING, |E|) bytes of E into the ring cells of positions -1, -2, ...; what
+//                     lies farther back is read from the dictionary itself, as far matches read the output (lz_decode.h).
+//                     A third template parameter: the instantiations without it are the code they were.
+//
 // LDS per wave: the tables of k_inflate (4 324 bytes) + the ring: 8 420 with the 4 KiB ring, 37 092 with the 32 KiB ring
 // (fewer than 1 024 items), 4 324 without one.  DESIGN.md 3.5 has the resource lines.
 #include "lz_common.h"
@@ -32,6 +39,14 @@ struct InfBatch {
     uint64_t *out_bytes; uint32_t *status, *failed;
     const uint32_t *order;                     // workgroup j takes item order[j]; NULL: item j
     uint32_t container;
+};
+
+// the call's preset dictionary as the DICT kernels see it; nothing where there is none
+template <bool DICT> struct InfDict {};
+template <> struct InfDict<true> {
+    const uint8_t *end;                        // behind the dictionary's last byte
+    uint32_t n;                                // |E| = min(dict_bytes, 32 768)
+    const uint32_t *adler;                     // Adler-32 of the whole dictionary (zlib container; NULL for raw)
 };
 
 __device__ __forceinline__ uint32_t infb_class(uint64_t bytes)
@@ -60,9 +75,9 @@ void k_batch_scatter(const uint64_t *__restrict__ in_bytes, uint32_t count, uint
     if (i < count) order[atomicAdd(&cursor[infb_class(in_bytes[i])], 1u)] = i;       // (< count: the cursors partition [0, count))
 }
 
-template <uint32_t RING, bool COUNT_ONLY>
+template <uint32_t RING, bool COUNT_ONLY, bool DICT = false>
 __global__ __launch_bounds__(64)
-void k_inflate_batch(InfBatch b)
+void k_inflate_batch(InfBatch b, InfDict<DICT> dd)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_ring[COUNT_ONLY ? 16u : RING];
     __shared__ uint16_t s_llut[1 << INF_LL_BITS], s_dlut[1 << INF_D_BITS];
@@ -82,15 +97,23 @@ void k_inflate_batch(InfBatch b)
         // ---- header and trailer: every lane reads the same few bytes, all inside [in, in + nb)
         bool bad = false;
         auto byte = [&](uint64_t i) -> uint32_t { if (i >= nb) { bad = true; return 0u; } return in[i]; };
-        const uint64_t hb = inf_header_bytes(b.container, byte, bad);
+        bool fdict = false;
+        uint32_t dictid = 0, dn = 0;                                    // dn: |E| for an item that uses the dictionary
+        const uint64_t hb = inf_header_bytes<DICT>(b.container, byte, bad, &fdict, &dictid);
+        const uint8_t *dend = nullptr;
+        if constexpr (DICT) {
+            dend = dd.end;
+            if (b.container == MI_CONTAINER_RAW) dn = dd.n;
+            else if (fdict && !bad) { if (dictid == *dd.adler) dn = dd.n; else bad = true; }    // another dictionary's stream
+        }
         const uint64_t tl = b.container == MI_CONTAINER_GZIP ? 8u : b.container == MI_CONTAINER_ZLIB ? 4u : 0u;
         if (bad || hb + tl >= nb) st = MI_ERR_CORRUPT;                  // (no room for one byte of DEFLATE data)
         else {
             // the DEFLATE data lies between header and trailer and ends, padded, exactly where the trailer starts
             const uint64_t nbits = 8ull * (nb - hb - tl);
             OutRing<RING> ring;
-            const InfWalk w = inf_blocks<RING, true, COUNT_ONLY>(in, 8ull * hb, nbits, out, (uint32_t)cap, true, ring, s_ring, s_llut,
-                                                                 s_dlut, s_ll, s_dc, s_len, s_cl, lane);
+            const InfWalk w = inf_blocks<RING, true, COUNT_ONLY, DICT>(in, 8ull * hb, nbits, out, (uint32_t)cap, true, ring, s_ring, s_llut,
+                                                                       s_dlut, s_ll, s_dc, s_len, s_cl, lane, dend, dn);
             if (w.big) st = MI_ERR_ARG;                                 // more than 2^31 - 1 bytes: not a batch item
             else if (w.bad || !w.final_seen || ((w.pos + 7u) & ~7ull) != nbits) st = MI_ERR_CORRUPT;
             else {
@@ -159,9 +182,11 @@ void k_inflate_batch_check(InfBatch b)
 
 static mi_status batch_launch(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in, const uint64_t *d_in_bytes,
                               void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes, uint32_t *d_status,
-                              uint32_t *d_failed, uint32_t flags, hipStream_t s, bool count_only)
+                              uint32_t *d_failed, uint32_t flags, hipStream_t s, bool count_only, const uint8_t *d_dict = nullptr,
+                              uint64_t dict_bytes = 0)
 {
     if (!ctx || container > MI_CONTAINER_GZIP || (flags & ~MI_INFLATE_NO_CHECKSUM) || count > 0x7FFFFFFFull) return MI_ERR_ARG;
+    if (dict_bytes && (!d_dict || container == MI_CONTAINER_GZIP || dict_bytes > INFB_MAX_BYTES)) return MI_ERR_ARG;   // gzip has no FDICT
     if (count == 0) return MI_OK;
     if (!d_in || !d_in_bytes || !d_out_bytes || !d_status || (!count_only && (!d_out || !d_out_cap))) return MI_ERR_ARG;
     const uint32_t cnt = (uint32_t)count;
@@ -170,9 +195,17 @@ static mi_status batch_launch(mi_ctx *ctx, uint32_t container, uint64_t count, c
     const char *e = getenv("MI_INFLATE_BATCH_ORDER");
     const bool ordered = e && atoi(e) != 0;
     uint32_t *head = nullptr, *order = nullptr;              // head: hist[64], cursor[64]
-    const mi_status st = ordered ? mi_ws_carve(ctx, [&](mi_carver &cv) { cv.take(head, INFB_WS_HEAD / 4); cv.take(order, cnt); })
-                                 : MI_OK;                    // (allocates and synchronises only while it grows)
+    // DICTID: the Adler-32 of the whole dictionary, on the stream, its partials and its result in the workspace
+    const bool dict = dict_bytes != 0, dsum = dict && container == MI_CONTAINER_ZLIB;
+    uint8_t *zws = nullptr;
+    uint32_t *d_adler = nullptr;
+    const mi_status st = ordered || dsum ? mi_ws_carve(ctx, [&](mi_carver &cv) {
+                                               if (ordered) { cv.take(head, INFB_WS_HEAD / 4); cv.take(order, cnt); }
+                                               if (dsum) { cv.take(zws, defz_ws_bytes()); cv.take(d_adler, 1); }
+                                           })
+                                         : MI_OK;            // (allocates and synchronises only while it grows)
     if (st) return st;
+    if (dsum) { const mi_status sd = defz_checksum(ctx, false, d_dict, dict_bytes, zws, d_adler, s); if (sd) return sd; }
     if (d_failed) MI_HIP(ctx, hipMemsetAsync(d_failed, 0, 4, s));
     if (ordered) {
         uint32_t *hist = head, *cursor = hist + 64;
@@ -188,9 +221,14 @@ static mi_status batch_launch(mi_ctx *ctx, uint32_t container, uint64_t count, c
         // the ring: as mi_inflate_dev — few items cannot fill the CUs anyway and get the whole 32 KiB window in LDS
         const char *r = getenv("MI_LZ_DECODE_RING");
         const uint32_t want = r ? (uint32_t)atoi(r) : (cnt < 1024u ? 32768u : 4096u);
-        if (count_only) hipLaunchKernelGGL((k_inflate_batch<4096u, true>), dim3(cnt), dim3(64), 0, s, b);
-        else if (want <= 4096u) hipLaunchKernelGGL((k_inflate_batch<4096u, false>), dim3(cnt), dim3(64), 0, s, b);
-        else hipLaunchKernelGGL((k_inflate_batch<32768u, false>), dim3(cnt), dim3(64), 0, s, b);
+        if (dict) {
+            const InfDict<true> dd{d_dict + dict_bytes, (uint32_t)(dict_bytes < 32768u ? dict_bytes : 32768u), d_adler};
+            if (count_only) hipLaunchKernelGGL((k_inflate_batch<4096u, true, true>), dim3(cnt), dim3(64), 0, s, b, dd);
+            else if (want <= 4096u) hipLaunchKernelGGL((k_inflate_batch<4096u, false, true>), dim3(cnt), dim3(64), 0, s, b, dd);
+            else hipLaunchKernelGGL((k_inflate_batch<32768u, false, true>), dim3(cnt), dim3(64), 0, s, b, dd);
+        } else if (count_only) hipLaunchKernelGGL((k_inflate_batch<4096u, true>), dim3(cnt), dim3(64), 0, s, b, InfDict<false>{});
+        else if (want <= 4096u) hipLaunchKernelGGL((k_inflate_batch<4096u, false>), dim3(cnt), dim3(64), 0, s, b, InfDict<false>{});
+        else hipLaunchKernelGGL((k_inflate_batch<32768u, false>), dim3(cnt), dim3(64), 0, s, b, InfDict<false>{});
     }
     if (!count_only && container != MI_CONTAINER_RAW && !(flags & MI_INFLATE_NO_CHECKSUM)) {
         mi_prof_scope pr(ctx, "k_inflate_batch_check", s, 0);
@@ -214,4 +252,23 @@ extern "C" mi_status mi_inflate_batch_size_dev(mi_ctx *ctx, uint32_t container, 
 {
     return batch_launch(ctx, container, count, d_in, d_in_bytes, nullptr, nullptr, d_out_bytes, d_status, d_failed, flags,
                         (hipStream_t)stream, true);
+}
+
+// One preset dictionary for the call (include/mi_codec.h).  dict_bytes == 0 is the call without one.
+extern "C" mi_status mi_inflate_batch_dict_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in,
+                                               const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap,
+                                               uint64_t *d_out_bytes, uint32_t *d_status, uint32_t *d_failed, const uint8_t *d_dict,
+                                               uint64_t dict_bytes, uint32_t flags, void *stream)
+{
+    return batch_launch(ctx, container, count, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, d_failed, flags,
+                        (hipStream_t)stream, false, d_dict, dict_bytes);
+}
+
+extern "C" mi_status mi_inflate_batch_dict_size_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in,
+                                                    const uint64_t *d_in_bytes, uint64_t *d_out_bytes, uint32_t *d_status,
+                                                    uint32_t *d_failed, const uint8_t *d_dict, uint64_t dict_bytes, uint32_t flags,
+                                                    void *stream)
+{
+    return batch_launch(ctx, container, count, d_in, d_in_bytes, nullptr, nullptr, d_out_bytes, d_status, d_failed, flags,
+                        (hipStream_t)stream, true, d_dict, dict_bytes);
 }

@@ -119,14 +119,19 @@ __device__ __forceinline__ void inf_dist_of(uint32_t c, uint32_t &base, uint32_t
 // The container header in front of the DEFLATE data, read through byte(i) (which flags what lies past the stream): its
 // length; `bad` is set where it is not one this library reads.  raw none; zlib CM = 8, CINFO <= 7, FCHECK, FDICT = 0; gzip
 // 1F 8B, CM = 8, reserved flag bits zero, FEXTRA / FNAME / FCOMMENT / FHCRC skipped by their lengths (FHCRC not verified).
-template <typename B>
-__device__ __forceinline__ uint64_t inf_header_bytes(uint32_t container, B &&byte, bool &bad)
+// With DICT (the caller holds a preset dictionary) a zlib header may have FDICT = 1: it is then 6 bytes, *fdict is set and
+// *dictid gets the four bytes behind FLG, big-endian; whether they name the caller's dictionary is the caller's to check.
+template <bool DICT = false, typename B>
+__device__ __forceinline__ uint64_t inf_header_bytes(uint32_t container, B &&byte, bool &bad, bool *fdict = nullptr, uint32_t *dictid = nullptr)
 {
     uint64_t hb = 0;
     if (container == MI_CONTAINER_ZLIB) {
         const uint32_t cmf = byte(0), flg = byte(1);
-        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u || (flg & 0x20u)) bad = true;
+        if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u || (!DICT && (flg & 0x20u))) bad = true;
         hb = 2;
+        if constexpr (DICT) {
+            if (flg & 0x20u) { *fdict = true; *dictid = (byte(2) << 24) | (byte(3) << 16) | (byte(4) << 8) | byte(5); hb = 6; }
+        }
     } else if (container == MI_CONTAINER_GZIP) {
         const uint32_t flg = byte(3);
         if (byte(0) != 0x1Fu || byte(1) != 0x8Bu || byte(2) != 8u || (flg & 0xE0u)) bad = true;
@@ -151,15 +156,24 @@ struct InfWalk {
 // through `ring`.  may_end: a block with BFINAL = 1 may close the range.  Every control value is wave-uniform (lz_decode.h): the
 // only memory on a token's critical path is its LUT cell.  The caller checks how the range ended (pos, o, final_seen) and
 // calls ring.finish.
-template <uint32_t RING, bool FLIP, bool COUNT_ONLY>
+// DICT (a FLIP mode): the `dn` <= 32 768 bytes that end at `dend` lie in front of the output as a preset dictionary — a
+// distance may be up to o + dn, in all three modes, and positions below 0 are dictionary bytes (OutRing::copy_dict).
+// dn = 0: a range that does not use the dictionary, decoded as without DICT.
+template <uint32_t RING, bool FLIP, bool COUNT_ONLY, bool DICT = false>
 __device__ __forceinline__ InfWalk inf_blocks(const uint8_t *__restrict__ stream, uint64_t rb, uint64_t nbits, uint8_t *outp, uint32_t n,
                                               bool may_end, OutRing<RING> &ring, uint8_t *s_ring, uint16_t *s_llut, uint16_t *s_dlut,
-                                              InfCode<288> &s_ll, InfCode<32> &s_dc, uint8_t *s_len, uint8_t *s_cl, uint32_t lane)
+                                              InfCode<288> &s_ll, InfCode<32> &s_dc, uint8_t *s_len, uint8_t *s_cl, uint32_t lane,
+                                              const uint8_t *dend = nullptr, uint32_t dn = 0)
 {
     static_assert(FLIP || !COUNT_ONLY, "counting is a FLIP mode");
+    static_assert(FLIP || !DICT, "a dictionary is a FLIP mode");
     BitsLsb br;
     br.init(stream, rb, nbits, lane);
     ring.init(s_ring, outp, lane);
+    if constexpr (DICT && !COUNT_ONLY) {
+        ring.preload(dend, dn);
+        __builtin_amdgcn_wave_barrier();
+    }
     uint64_t pos = 0;
     uint32_t o = 0;
     bool bad = false, fixed_built = false, final_seen = false, counting = COUNT_ONLY, big = false;
@@ -295,9 +309,10 @@ __device__ __forceinline__ InfWalk inf_blocks(const uint8_t *__restrict__ stream
                     const uint32_t d = base + br.peek(nb);              // <= 15 + 13 bits since the refill
                     br.skip(nb); pos += nb;
                     if constexpr (FLIP) {
-                        if (d > o) { bad = true; break; }               // before the range's first byte
+                        if (d > o + (DICT ? dn : 0u)) { bad = true; break; }    // before the range's first byte (the dictionary's)
                         if (!COUNT_ONLY && !counting && len > n - o) counting = true;   // a match is written whole or not at all
                         if (COUNT_ONLY || counting) { if (len > INF_MAX_POS - o) { bad = true; big = true; break; } }
+                        else if (DICT && d > o) ring.copy_dict(o, d, len, dend);
                         else ring.copy(o, d, len);
                     } else {
                         if (d > o || len > n - o) { bad = true; break; }    // before the segment's first byte / past its last

@@ -59,7 +59,8 @@ mi_status mi_deflate_h_decode_launch(mi_ctx *ctx, const mi_lz_params *p, const u
 
 // ---- defz.hip: mode Z (standard DEFLATE) — the entropy stage, the container's prologue (checksum) and epilogue
 void      defz_launch_encode(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_in, uint64_t n,
-                             uint32_t block, uint64_t b0, uint32_t nb, bool desc, hipStream_t s);     // desc: d_in is a descriptor table
+                             uint32_t block, uint64_t b0, uint32_t nb, bool desc, hipStream_t s, bool dict = false);
+                             // desc: d_in is a descriptor table; dict: whose blocks may begin with bytes that are not the item's (LzBlkDesc.skip)
 uint32_t  defz_header_bytes(uint32_t container);
 uint32_t  defz_trailer_bytes(uint32_t container);
 size_t    defz_ws_bytes();                                             // the checksum partials
@@ -81,13 +82,29 @@ struct DfbCall {
     uint32_t container; uint64_t count, max_blocks;
     const void *const *in; const uint64_t *in_bytes; void *const *out; const uint64_t *out_cap;
     uint64_t *out_bytes; uint32_t *status, *failed;
+    // a preset dictionary (mi_deflate_batch_dict_dev; all zero without one).  ulen = |U|, the bytes of its tail an item's first block
+    // is staged behind: that block holds block - ulen bytes of the item, the later ones `block` each (dfb_first / dfb_nblk below)
+    const uint8_t *dict; uint64_t dict_bytes; uint32_t ulen;
+    // the staging cells, filled in by lz_encode_impl once the pipeline's batches are known: block g of the table is block g % nbmax of
+    // pipeline batch g / nbmax, which runs on scratch set (g / nbmax) % nsets — its cell is stage[that set] + (g % nbmax) * block
+    uint32_t nbmax, nsets; uint8_t *stage[MI_SETS];
 };
+// the block layout of an item of nb bytes: bytes in its first block, its blocks, where block k starts and ends
+__host__ __device__ static inline uint64_t dfb_first(uint64_t nb, uint32_t block, uint32_t ulen) { return nb < block - ulen ? nb : block - ulen; }
+__host__ __device__ static inline uint64_t dfb_nblk(uint64_t nb, uint32_t block, uint32_t ulen)
+{
+    return nb == 0 ? 0 : 1u + (nb - dfb_first(nb, block, ulen) + block - 1u) / block;
+}
+__host__ __device__ static inline uint64_t dfb_begin_of(uint64_t k, uint32_t block, uint32_t ulen) { return k ? (uint64_t)(block - ulen) + (k - 1u) * block : 0; }
 #define DFB_MAX_BYTES 0x7FFFFFFFull            // per item and per count: block numbers and positions inside an item are 32-bit
 size_t    dfb_ws_bytes(const DfbCall &b);
 mi_status dfb_begin(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s, const uint8_t **desc);
 void      dfb_launch_place(const DfbCall &b, void *ws, const uint32_t *slots, const uint64_t *block_bits, uint64_t b0, uint32_t nb,
                            uint64_t seq, hipStream_t s);
 mi_status dfb_end(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s);
+void      dfb_launch_stage(const DfbCall &b, uint32_t block, void *ws, uint64_t b0, uint32_t nb, hipStream_t s);   // U and the items' heads -> the cells
+uint32_t  dfb_ulen(uint64_t dict_bytes, uint32_t block);                                                           // |U| = min(dict_bytes, 32 768, block / 2)
+size_t    dfb_stage_bytes(const DfbCall &b, uint32_t nbmax, uint32_t block);                                       // per scratch set; 0 without a dictionary
 
 // ---- inflate_batch.hip: the per-item limit
 #define INFB_MAX_BYTES 0x7FFFFFFFull           // per item, compressed and inflated: positions inside an item are 32-bit

@@ -70,8 +70,11 @@ struct LzBlkDesc {
     uint32_t n;            // its bytes, 1..block
     uint32_t item;         // the item it belongs to; LZ_DESC_PAD: a pad block behind the batch's real ones (one zero byte, placed nowhere)
     uint32_t blk;          // its number inside the item
-    uint32_t last;         // 1: the item's last block
+    uint16_t last;         // 1: the item's last block
+    uint16_t skip;         // bytes in front of the item's own: a preset dictionary's tail, staged with the item's head (an item's first block
+                           // under mi_deflate_batch_dict_dev, else 0).  The finder sees all n bytes; tokens start at `skip`
 };
+static_assert(sizeof(LzBlkDesc) == 24, "the table's stride");
 #define LZ_DESC_PAD 0xFFFFFFFFu
 
 template <bool DESC>
@@ -86,6 +89,14 @@ __device__ __forceinline__ void lz_block_src(const uint8_t *__restrict__ in, uin
         n = (uint32_t)((n_total - off) < block ? (n_total - off) : block);
         src = in + off;
     }
+}
+
+// what of a descriptor's block is the item's own: 0 unless DICT (the kernels behind the finder, which work on the item's bytes)
+template <bool DICT>
+__device__ __forceinline__ uint32_t lz_block_skip(const uint8_t *__restrict__ in, uint64_t block0, uint32_t lb)
+{
+    if constexpr (DICT) return reinterpret_cast<const LzBlkDesc *>(in)[block0 + lb].skip;
+    else return 0u;
 }
 
 // per-block record written by k_lz_sort_home

@@ -105,6 +105,34 @@ struct OutRing {
             for (uint32_t j = lane; j < take; j += 64u) ring[(o + j) & RM] = ring[(o - d + (j % d)) & RM];      // d < 64: near
         }
     }
+    // ---- a preset dictionary in front of position 0 (inflate_batch.hip).  Its last byte is position -1: `dend` points behind
+    // it, `dn` <= 32 768 is its length.  Positions stay uint32_t; a position below 0 is one with the top bit set, and
+    // -k & RM is the cell that position RING - k will overwrite, so the cell rule of fetch() holds for it once it is written
+    // without the wrap: cell valid while RING - k >= oend.
+    // the last min(RING, dn) bytes of the dictionary into the cells of positions -1, -2, ...: before the walk's first token
+    __device__ __forceinline__ void preload(const uint8_t *dend, uint32_t dn)
+    {
+        const uint32_t m = dn < RING ? dn : RING;
+        for (uint32_t k = 1u + lane; k <= m; k += 64u) ring[(0u - k) & RM] = dend[-(int64_t)k];
+    }
+    // byte at position x, which may lie in the dictionary (then 1 <= -x <= dn: the caller's distance rule)
+    __device__ __forceinline__ uint8_t fetch_dict(uint32_t x, uint32_t oend, const uint8_t *dend) const
+    {
+        if ((int32_t)x >= 0) return fetch(x, oend);
+        const uint32_t k = 0u - x;
+        if (k <= RING && RING - k >= oend) return ring[x & RM];       // preloaded and not yet overwritten
+        return dend[-(int64_t)k];
+    }
+    // copy() for a match that starts in the dictionary (o < d <= o + dn).  It may run into the output, and overlap itself
+    // across that seam (d < take).  The two all-in-the-ring forms of copy() index cells modulo RING and are right as they are:
+    // with d + take <= RING, or d < 64, every source cell is at most RING - take behind the write cursor and, where its
+    // position is below 0, preloaded (-x <= d <= RING).  Only the far form needs the dictionary itself.
+    __device__ __forceinline__ void copy_dict(uint32_t o, uint32_t d, uint32_t take, const uint8_t *dend)
+    {
+        const uint32_t oend = o + take;
+        if (d + take <= RING || (d < take && d < 64u)) copy(o, d, take);
+        else for (uint32_t j = lane; j < take; j += 64u) ring[(o + j) & RM] = fetch_dict(o - d + j, oend, dend);
+    }
     __device__ __forceinline__ void copy_out(uint32_t from, uint32_t to)
     {
         if (aligned && !((from | to) & 15u)) {

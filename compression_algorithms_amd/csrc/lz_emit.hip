@@ -21,7 +21,9 @@
 #include <stdlib.h>
 
 
-template <bool DESC>                                 // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
+// DICT (with DESC): the first `skip` bytes of the block (LzBlkDesc) are a preset dictionary's tail — there for the finder, whose
+// candidates may point into it, and no part of the item: the parse starts at `skip` and only the item's tokens are counted and emitted
+template <bool DESC, bool DICT = false>              // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
 __global__ __launch_bounds__(1024)
 void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, LzScratch sc, Lz2Scratch s2, int use_v2,
                      uint64_t block0, uint32_t *__restrict__ trec_all)
@@ -40,7 +42,9 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     long long tk = clock64();
 #define PE_TICK(k) do { if (s2.dbg && tid == 0) { long long t2 = clock64(); atomicAdd((unsigned long long *)&s2.dbg[16 + (k)], (unsigned long long)(t2 - tk)); tk = t2; } } while (0)
     const uint8_t *src; uint32_t n;
+    static_assert(DESC || !DICT, "a dictionary's tail comes with a descriptor");
     lz_block_src<DESC>(in, n_total, P.block, block0, lb, src, n);
+    const uint32_t skip = lz_block_skip<DICT>(in, block0, lb);
     const uint16_t *cand = sc.cand + (size_t)lb * LZ_MAX_BLOCK;
     const uint32_t W = 1u << P.wbits, max_len = (1u << P.lbits) - 1u;
 
@@ -176,6 +180,11 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
         for (uint32_t p = tid; p < n; p += 1024u) s_L[p] = (uint8_t)token_len(p, cand[p]);
     }
     __syncthreads();
+    if constexpr (DICT) {
+        // no token starts in front of the item: the exit chain walks to `skip` one position at a time and is greedy from there
+        for (uint32_t p = tid; p < skip; p += 1024u) s_L[p] = 0;
+        __syncthreads();
+    }
 
     PE_TICK(1);
     // ---- B: exit offset of every position of a 64-position chunk into the next chunk
@@ -240,6 +249,10 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
                     o += l ? l : 1u;
                 }
             }
+            if constexpr (DICT) {                                   // the positions in front of the item are no tokens of its
+                const uint64_t keep = c * 64u >= skip ? ~0ull : c * 64u + 64u <= skip ? 0ull : ~0ull << (skip - c * 64u);
+                tok &= keep; mat &= keep;
+            }
             s_tok[c] = tok; s_mat[c] = mat;
         } else {
             s_tok[c] = 0; s_mat[c] = 0;
@@ -248,7 +261,7 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     __syncthreads();
     if (wide && tid == 0) {
         // lbits > 5: a plain serial walk (not a reference configuration; kept for completeness)
-        uint32_t p = 0;
+        uint32_t p = DICT ? skip : 0u;
         while (p < n) {
             const uint32_t l = s_L[p];
             s_tok[p >> 6] |= 1ull << (p & 63u);
@@ -562,11 +575,13 @@ static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, 
 
 // The pipeline's workspace: the scratch sets (lz_carve), then the output's running bit position, the token records of every
 // form but LZ_TOKENS (one array per set), and what the form keeps for itself (mode Z: the checksum's partials; a batch: its tables)
-struct LzWs { LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS]; uint64_t *base_bits; uint32_t *trec; void *zws; };
+struct LzWs { LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS]; uint64_t *base_bits; uint32_t *trec; void *zws; uint8_t *stage[MI_SETS]; };
 
-static void lz_carve_all(mi_carver &cv, uint32_t nb, int nsets, size_t trec_words, size_t z_bytes, LzWs *w)
+// stage_bytes: a batch with a preset dictionary stages its items' first blocks behind the dictionary's tail, one cell per block slot of a set
+static void lz_carve_all(mi_carver &cv, uint32_t nb, int nsets, size_t trec_words, size_t z_bytes, size_t stage_bytes, LzWs *w)
 {
     for (int k = 0; k < nsets; ++k) lz_carve(cv, nb, &w->sc[k], &w->sc2[k]);
+    for (int k = 0; k < MI_SETS; ++k) w->stage[k] = k < nsets && stage_bytes ? cv.take<uint8_t>(stage_bytes) : nullptr;
     w->base_bits = reinterpret_cast<uint64_t *>(cv.take<uint8_t>(8192));
     w->trec = trec_words ? cv.take<uint32_t>(trec_words) : nullptr;
     w->zws = cv.take<uint8_t>(z_bytes);
@@ -651,15 +666,20 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
     const int nsets = overlap ? MI_SETS : 1;
     const size_t trec_words = c.form == LZ_TOKENS ? 0 : (size_t)nbmax * LZ_MAX_BLOCK * nsets;
     const size_t z_bytes = items ? dfb_ws_bytes(*c.batch) : (c.form == LZ_Z || c.form == LZ_BGZF) ? defz_ws_bytes() : 0;
+    const bool dict = items && c.batch->ulen != 0;                 // a preset dictionary: items' first blocks are staged behind its tail
+    const size_t stage_bytes = dict ? dfb_stage_bytes(*c.batch, nbmax, P.block) : 0;
     LzWs t;
-    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve_all(cv, nbmax, nsets, trec_words, z_bytes, &t); });
+    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve_all(cv, nbmax, nsets, trec_words, z_bytes, stage_bytes, &t); });
     if (st) return st;
+    DfbCall bc = items ? *c.batch : DfbCall{};                     // the batch with its staging cells in place
+    bc.nbmax = nbmax; bc.nsets = (uint32_t)nsets;
+    for (int k = 0; k < MI_SETS; ++k) bc.stage[k] = t.stage[k];
     const LzScratch *sc = t.sc; const Lz2Scratch *sc2 = t.sc2;
     // in front of the first block: where the output's bits start, and what the form needs before its blocks
     switch (c.form) {
     case LZ_TOKENS: case LZ_H: MI_HIP(ctx, hipMemsetAsync(t.base_bits, 0, 8, s)); break;
     case LZ_Z: case LZ_BGZF:   st = defz_begin(ctx, c.container, d_in, n, d_out, t.base_bits, t.zws, s); break;   // (the base starts at the header's bits)
-    case LZ_BATCH:             st = dfb_begin(ctx, *c.batch, P.block, t.zws, s, &d_in); break;                    // (d_in: the descriptor table from here on)
+    case LZ_BATCH:             st = dfb_begin(ctx, bc, P.block, t.zws, s, &d_in); break;                          // (d_in: the descriptor table from here on)
     }
     if (st) return st;
     // behind the last block.  The table of an empty input is its one closing entry (mode Z's epilogue writes it itself, a batch
@@ -670,7 +690,7 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         case LZ_TOKENS: case LZ_H: return MI_OK;
         case LZ_Z:                 return defz_end(ctx, c.container, d_out, d_block_bits, nblocks, n, t.zws, c.d_out_bytes, s);
         case LZ_BGZF:              return bgzf_end(ctx, d_out, d_block_bits, nblocks, c.d_out_bytes, s);
-        case LZ_BATCH:             return dfb_end(ctx, *c.batch, P.block, t.zws, s);
+        case LZ_BATCH:             return dfb_end(ctx, bc, P.block, t.zws, s);
         }
         return MI_ERR_ARG;
     };
@@ -683,19 +703,20 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         uint32_t *trec = t.trec ? t.trec + (size_t)k * nbmax * LZ_MAX_BLOCK : nullptr;
         {
             mi_prof_scope pr(ctx, "k_lz_parse_emit", sp, pbytes);
-            if (items) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
+            if (dict) hipLaunchKernelGGL((k_lz_parse_emit<true, true>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
+            else if (items) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
             else hipLaunchKernelGGL(k_lz_parse_emit<false>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
         }
         auto defh = [&] { mi_prof_scope ph(ctx, "k_defh_encode", sp, pbytes);     // mode H's entropy stage, the scan inside it: straight into the stream
                           defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, t.base_bits, d_block_bits + b0, d_out, cap_bytes, sp); };
         auto defz = [&] { mi_prof_scope ph(ctx, "k_defz_encode", sp, pbytes);     // mode Z's entropy stage: records in their slots
-                          defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, items, sp); };
+                          defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, items, sp, dict); };
         auto frame = [&] { mi_prof_scope pf(ctx, "k_bgzf_frame", sp, pbytes);     // every record a gzip member
                            bgzf_launch_frame(sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp); };
         // every record to its own item (batches reach this stream in order: the item that straddles two of them goes on where the
         // one before stopped)
         auto place = [&] { mi_prof_scope pl(ctx, "k_dfb_place", sp, pbytes);
-                           dfb_launch_place(*c.batch, t.zws, sc[k].slot, sc[k].block_bits, b0, nb, seq, sp); };
+                           dfb_launch_place(bc, t.zws, sc[k].slot, sc[k].block_bits, b0, nb, seq, sp); };
         auto concat = [&] {                                        // the slots' contents into the one output stream: scan, then concatenate
             hipLaunchKernelGGL(k_lz_scan_blocks, dim3(1), dim3(256), 0, sp, sc[k].block_bits, nb, t.base_bits, excl_local, d_block_bits + b0);
             mi_prof_scope pr(ctx, "k_lz_concat", sp, pbytes);
@@ -726,6 +747,9 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         nb = (uint32_t)(nblocks - b0 < nbmax ? nblocks - b0 : nbmax);
         const int k = (int)(batch % (uint64_t)nsets);
         if (overlap && batch >= (uint64_t)nsets) MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_done[k], 0));   // set k is free again
+        // a dictionary's tail and the items' heads into this set's cells: on `s`, in front of everything that reads a block (the other
+        // streams fork from `s` behind it), and behind the wait above for the batch that used the cells last
+        if (dict) { mi_prof_scope pr(ctx, "k_dfb_stage", s, (uint64_t)nb * P.block); dfb_launch_stage(bc, P.block, t.zws, b0, nb, s); }
         // stage A: partition + find on `s`, the fallback chain and the wide finder beside them
         const hipStream_t sf = !overlap ? (solo ? ctx->fb : s) : (batch & 1u) ? sf_odd : ctx->fb;
         st = lz_find_stage_a(ctx, P, d_in, n, b0, nb, sc[k], sc2[k], s, sf, ctx->ev_part[k], ctx->ev_fb[k], ctx->ev_wide[k]);

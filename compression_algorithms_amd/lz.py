@@ -736,22 +736,48 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr() if t.numel() else 0)
 
 
-def _batch_sizes_dev(ctx, c, count, d_in, d_nb):
+def _zdict_check(zdict, c):
+    """a preset dictionary (zlib's zdict: bytes or a uint8 tensor, or None) and the container: what can be refused without a device"""
+    if zdict is None:
+        return
+    if torch.is_tensor(zdict):
+        if zdict.dtype != torch.uint8 or zdict.dim() != 1:
+            raise ValueError("zdict: bytes or a one-dimensional uint8 tensor")
+    elif not isinstance(zdict, (bytes, bytearray, memoryview)):
+        raise ValueError("zdict: bytes or a one-dimensional uint8 tensor")
+    if _nbytes(zdict) and c == CONTAINERS["gzip"]:
+        raise ValueError("gzip has no dictionary field: a preset dictionary goes with the raw or the zlib container")
+
+
+def _zdict_dev(ctx, zdict):
+    """-> the dictionary as a contiguous uint8 tensor on the context's device"""
+    if torch.is_tensor(zdict):
+        return zdict.to(device=ctx.device).contiguous()
+    return as_device_bytes(bytes(zdict), ctx.device) if len(zdict) else torch.zeros(0, dtype=torch.uint8, device=ctx.device)
+
+
+def _batch_sizes_dev(ctx, c, count, d_in, d_nb, d_dict=None):
     sizes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
     status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
-    st = ctx.L.mi_inflate_batch_size_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(sizes), _ptr(status), None, 0, ctx.stream_ptr())
-    _lib.check(st, "mi_inflate_batch_size_dev")
+    if d_dict is None:
+        st = ctx.L.mi_inflate_batch_size_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(sizes), _ptr(status), None, 0, ctx.stream_ptr())
+        _lib.check(st, "mi_inflate_batch_size_dev")
+    else:
+        st = ctx.L.mi_inflate_batch_dict_size_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(sizes), _ptr(status), None, _ptr(d_dict),
+                                                  d_dict.numel(), 0, ctx.stream_ptr())
+        _lib.check(st, "mi_inflate_batch_dict_size_dev")
     return sizes[:count], status[:count]
 
 
-def inflate_batch_sizes(items, container="gzip", ctx=None):
+def inflate_batch_sizes(items, container="gzip", ctx=None, zdict=None):
     """What every item of a batch inflates to, without writing a byte -> (sizes int64, status int32) device tensors.  `items`
-    as for inflate_batch.  A checksum mismatch cannot be seen here (such an item is MI_OK)."""
+    and `zdict` as for inflate_batch.  A checksum mismatch cannot be seen here (such an item is MI_OK)."""
     off, count = _batch_check(items, None)
     c = CONTAINERS.get(container, container)
+    _zdict_check(zdict, c)
     ctx = ctx or default_context()
     keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
-    out = _batch_sizes_dev(ctx, c, count, d_in, d_nb)
+    out = _batch_sizes_dev(ctx, c, count, d_in, d_nb, None if zdict is None else _zdict_dev(ctx, zdict))
     ctx.sync()                                                 # (the inputs in `keep` may go now)
     return out
 
@@ -771,19 +797,23 @@ class InflateBatch:
         return self
 
 
-def inflate_batch(items, container="gzip", caps=None, verify=True, ctx=None):
+def inflate_batch(items, container="gzip", caps=None, verify=True, ctx=None, zdict=None):
     """Inflate many independent streams of one container ("raw", "zlib", "gzip") in one launch -> InflateBatch.
 
     items: a list of bytes or uint8 tensors, or a pair (buffer, offsets) for a packed buffer with count + 1 offsets (item i
     is buffer[offsets[i]:offsets[i + 1]]: no alignment needed).  caps: the output capacity of every item (list or tensor);
     None runs the size pass first and allocates one packed output.  An item that does not fit its capacity comes back
-    MI_ERR_CAPACITY with out_bytes = the size it needs; one bad item does not spoil the rest."""
+    MI_ERR_CAPACITY with out_bytes = the size it needs; one bad item does not spoil the rest.  zdict: one preset dictionary
+    for all items (bytes or a uint8 device tensor), as zlib.decompressobj(wbits, zdict=...) takes it: every raw item uses
+    it, a zlib item if its header names it (FDICT and the dictionary's Adler-32); gzip has no such field and is refused."""
     off, count = _batch_check(items, caps)
     c = CONTAINERS.get(container, container)
+    _zdict_check(zdict, c)
     ctx = ctx or default_context()
     keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    d_dict = None if zdict is None else _zdict_dev(ctx, zdict)
     if caps is None:
-        d_cap = _batch_sizes_dev(ctx, c, count, d_in, d_nb)[0]
+        d_cap = _batch_sizes_dev(ctx, c, count, d_in, d_nb, d_dict)[0]
         cap = [int(v) for v in d_cap.cpu()]
     else:
         cap = [int(v) for v in (caps.cpu().tolist() if torch.is_tensor(caps) else caps)]
@@ -797,34 +827,48 @@ def inflate_batch(items, container="gzip", caps=None, verify=True, ctx=None):
     nbytes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
     status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
     failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
-    st = ctx.L.mi_inflate_batch_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(d_out), _ptr(d_cap), _ptr(nbytes), _ptr(status),
-                                    _ptr(failed), 0 if verify else MI_INFLATE_NO_CHECKSUM, ctx.stream_ptr())
-    _lib.check(st, "mi_inflate_batch_dev")
+    flags = 0 if verify else MI_INFLATE_NO_CHECKSUM
+    if d_dict is None:
+        st = ctx.L.mi_inflate_batch_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(d_out), _ptr(d_cap), _ptr(nbytes), _ptr(status),
+                                        _ptr(failed), flags, ctx.stream_ptr())
+        _lib.check(st, "mi_inflate_batch_dev")
+    else:
+        st = ctx.L.mi_inflate_batch_dict_dev(ctx.h, c, count, _ptr(d_in), _ptr(d_nb), _ptr(d_out), _ptr(d_cap), _ptr(nbytes), _ptr(status),
+                                             _ptr(failed), _ptr(d_dict), d_dict.numel(), flags, ctx.stream_ptr())
+        _lib.check(st, "mi_inflate_batch_dict_dev")
     ctx.sync()
     nb, stl = [int(v) for v in nbytes[:count].cpu()], [int(v) for v in status[:count].cpu()]
     outputs = [out[a:a + (n if s == 0 else 0)] for a, n, s in zip(offs, nb, stl)]
     return InflateBatch(outputs, nbytes[:count], status[:count], int(failed.item()) if count else 0)
 
 
-def inflate_batch_host(items, container="gzip", ctx=None, verify=True):
+def inflate_batch_host(items, container="gzip", ctx=None, verify=True, zdict=None):
     """the host-buffer entry point (mi_inflate_batch, called once for the sizes and once to inflate, so the inputs travel to
     the device twice: a convenience path): a list of bytes -> (list of bytes, None where the item failed; list of status
-    codes)"""
+    codes).  zdict: a preset dictionary as for inflate_batch, here host bytes (mi_inflate_batch_dict)"""
     items = [bytes(x) for x in items]
     count = len(items)
     c = CONTAINERS.get(container, container)
+    _zdict_check(zdict, c)
     ctx = ctx or default_context()
+    if zdict is not None:
+        hd = np.frombuffer(bytes(zdict.cpu().numpy().tobytes() if torch.is_tensor(zdict) else zdict), dtype=np.uint8)
+        hdp = hd.ctypes.data_as(C.c_void_p) if hd.size else None
     arrs = [np.frombuffer(b, dtype=np.uint8) for b in items]
     h_in = (C.c_void_p * max(count, 1))(*[a.ctypes.data if a.size else None for a in arrs])
     h_nb = (C.c_uint64 * max(count, 1))(*[a.size for a in arrs])
     sizes, status = (C.c_uint64 * max(count, 1))(), (C.c_uint32 * max(count, 1))()
     flags = 0 if verify else MI_INFLATE_NO_CHECKSUM
-    st = ctx.L.mi_inflate_batch(ctx.h, c, count, h_in, h_nb, None, None, sizes, status, flags)
+    if zdict is None:
+        call = lambda o, cp: ctx.L.mi_inflate_batch(ctx.h, c, count, h_in, h_nb, o, cp, sizes, status, flags)
+    else:
+        call = lambda o, cp: ctx.L.mi_inflate_batch_dict(ctx.h, c, count, h_in, h_nb, o, cp, sizes, status, hdp, hd.size, flags)
+    st = call(None, None)
     _lib.check(st, "mi_inflate_batch")
     outs = [np.zeros(max(int(sizes[i]), 1), dtype=np.uint8) for i in range(count)]
     h_out = (C.c_void_p * max(count, 1))(*[o.ctypes.data for o in outs])
     h_cap = (C.c_uint64 * max(count, 1))(*[int(sizes[i]) for i in range(count)])
-    st = ctx.L.mi_inflate_batch(ctx.h, c, count, h_in, h_nb, h_out, h_cap, sizes, status, flags)
+    st = call(h_out, h_cap)
     _lib.check(st, "mi_inflate_batch")
     return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]
 
@@ -843,14 +887,31 @@ class DeflateBatch(InflateBatch):
         return self
 
 
-def deflate_batch_max_blocks(total_bytes, count, p=None):
-    """mi_deflate_batch_max_blocks: an upper bound on the blocks of `count` items of `total_bytes` together"""
+def deflate_batch_max_blocks(total_bytes, count, p=None, dict_bytes=0):
+    """mi_deflate_batch_max_blocks: an upper bound on the blocks of `count` items of `total_bytes` together; dict_bytes: with a
+    preset dictionary of that size (mi_deflate_batch_dict_max_blocks: an item's first block is shorter by the dictionary's tail)"""
     p = p or params("deflate")
+    if dict_bytes:
+        return int(_lib.lib().mi_deflate_batch_dict_max_blocks(total_bytes, count, C.byref(p), dict_bytes))
     return int(_lib.lib().mi_deflate_batch_max_blocks(total_bytes, count, C.byref(p)))
 
 
-def deflate_batch(items, p=None, container="gzip", caps=None, ctx=None, max_blocks=None):
+def deflate_batch_bound_bytes(n, p=None, container="gzip", dict_bytes=0):
+    """mi_deflate_batch_dict_bound_bytes: the most an item of n bytes comes to, with a preset dictionary of dict_bytes"""
+    p = p or params("deflate")
+    return int(_lib.lib().mi_deflate_batch_dict_bound_bytes(n, C.byref(p), CONTAINERS.get(container, container), dict_bytes))
+
+
+def _dict_blocks(n, block, dict_bytes):
+    """the blocks of an item of n bytes behind a dictionary of dict_bytes (include/mi_codec.h)"""
+    u = min(dict_bytes, 32768, block // 2)
+    return 0 if n == 0 else 1 + (n - min(n, block - u) + block - 1) // block
+
+
+def deflate_batch(items, p=None, container="gzip", caps=None, ctx=None, max_blocks=None, zdict=None):
     """Compress many independent buffers in one call -> DeflateBatch.  Item i's stream is byte for byte compress_z(item i).
+    zdict: one preset dictionary for all items (bytes or a uint8 device tensor), as zlib.compressobj(..., zdict=...) takes it:
+    the streams are what zlib.decompressobj(wbits, zdict=...) and inflate_batch(..., zdict=...) read; raw or zlib only.
 
     items: a list of bytes or uint8 tensors, or a pair (buffer, offsets) for a packed buffer with count + 1 offsets (item i
     is buffer[offsets[i]:offsets[i + 1]]: no alignment needed), as for inflate_batch.  caps: the output capacity of every
@@ -861,12 +922,15 @@ def deflate_batch(items, p=None, container="gzip", caps=None, ctx=None, max_bloc
     c = CONTAINERS.get(container, container)
     if c not in CONTAINERS.values():
         raise ValueError(f"container {container!r}: one of {sorted(CONTAINERS)}")
+    _zdict_check(zdict, c)
     ctx = ctx or default_context()
     p = p or params("deflate")
     keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    d_dict = None if zdict is None else _zdict_dev(ctx, zdict)
+    nd = 0 if d_dict is None else d_dict.numel()
     sizes = [int(v) for v in d_nb.cpu()] if count else []
     if caps is None:
-        cap = [bound_bytes_z(n, p, c) for n in sizes]
+        cap = [bound_bytes_z(n, p, c) if d_dict is None else deflate_batch_bound_bytes(n, p, c, nd) for n in sizes]
     else:
         cap = [int(v) for v in (caps.cpu().tolist() if torch.is_tensor(caps) else caps)]
     d_cap = torch.tensor(cap, dtype=torch.int64, device=ctx.device) if count else torch.zeros(0, dtype=torch.int64, device=ctx.device)
@@ -877,14 +941,19 @@ def deflate_batch(items, p=None, container="gzip", caps=None, ctx=None, max_bloc
     out = torch.empty(max(at, 16), dtype=torch.uint8, device=ctx.device)
     d_out = torch.tensor([out.data_ptr() + a for a in offs], dtype=torch.int64, device=ctx.device) if count else d_cap
     if max_blocks is None:
-        max_blocks = sum((n + p.block - 1) // p.block for n in sizes if n <= 0x7FFFFFFF)
+        max_blocks = sum(_dict_blocks(n, p.block, nd) for n in sizes if n <= 0x7FFFFFFF)
     nbytes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
     status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
     failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
     v0 = ctx.order_violations()
-    st = ctx.L.mi_deflate_batch_dev(ctx.h, C.byref(p), c, count, _ptr(d_in), _ptr(d_nb), max_blocks, _ptr(d_out), _ptr(d_cap),
-                                    _ptr(nbytes), _ptr(status), _ptr(failed), ctx.stream_ptr())
-    _lib.check(st, "mi_deflate_batch_dev")
+    if d_dict is None:
+        st = ctx.L.mi_deflate_batch_dev(ctx.h, C.byref(p), c, count, _ptr(d_in), _ptr(d_nb), max_blocks, _ptr(d_out), _ptr(d_cap),
+                                        _ptr(nbytes), _ptr(status), _ptr(failed), ctx.stream_ptr())
+        _lib.check(st, "mi_deflate_batch_dev")
+    else:
+        st = ctx.L.mi_deflate_batch_dict_dev(ctx.h, C.byref(p), c, count, _ptr(d_in), _ptr(d_nb), max_blocks, _ptr(d_out), _ptr(d_cap),
+                                             _ptr(nbytes), _ptr(status), _ptr(failed), _ptr(d_dict), nd, ctx.stream_ptr())
+        _lib.check(st, "mi_deflate_batch_dict_dev")
     ctx.sync()
     if ctx.order_violations() != v0:
         raise _lib.MiError(10, "the encoder that wrote this batch reported a sort out of order")
@@ -893,22 +962,28 @@ def deflate_batch(items, p=None, container="gzip", caps=None, ctx=None, max_bloc
     return DeflateBatch(outputs, nbytes[:count], status[:count], int(failed.item()) if count else 0)
 
 
-def deflate_batch_host(items, p=None, container="gzip", ctx=None):
+def deflate_batch_host(items, p=None, container="gzip", ctx=None, zdict=None):
     """the host-buffer entry point (mi_deflate_batch): a list of bytes -> (list of bytes, None where the item failed; list of
-    status codes)"""
+    status codes).  zdict: a preset dictionary as for deflate_batch, here host bytes (mi_deflate_batch_dict)"""
     items = [bytes(x) for x in items]
     count = len(items)
     c = CONTAINERS.get(container, container)
+    _zdict_check(zdict, c)
     ctx = ctx or default_context()
     p = p or params("deflate")
+    hd = None if zdict is None else np.frombuffer(zdict.cpu().numpy().tobytes() if torch.is_tensor(zdict) else bytes(zdict), dtype=np.uint8)
     arrs = [np.frombuffer(b, dtype=np.uint8) for b in items]
     h_in = (C.c_void_p * max(count, 1))(*[a.ctypes.data if a.size else None for a in arrs])
     h_nb = (C.c_uint64 * max(count, 1))(*[a.size for a in arrs])
-    caps = [bound_bytes_z(a.size, p, c) for a in arrs]
+    caps = [bound_bytes_z(a.size, p, c) if hd is None else deflate_batch_bound_bytes(a.size, p, c, hd.size) for a in arrs]
     outs = [np.zeros(max(v, 1), dtype=np.uint8) for v in caps]
     h_out = (C.c_void_p * max(count, 1))(*[o.ctypes.data for o in outs])
     h_cap = (C.c_uint64 * max(count, 1))(*caps)
     sizes, status = (C.c_uint64 * max(count, 1))(), (C.c_uint32 * max(count, 1))()
-    st = ctx.L.mi_deflate_batch(ctx.h, C.byref(p), c, count, h_in, h_nb, h_out, h_cap, sizes, status)
+    if hd is None:
+        st = ctx.L.mi_deflate_batch(ctx.h, C.byref(p), c, count, h_in, h_nb, h_out, h_cap, sizes, status)
+    else:
+        st = ctx.L.mi_deflate_batch_dict(ctx.h, C.byref(p), c, count, h_in, h_nb, h_out, h_cap, sizes, status,
+                                         hd.ctypes.data_as(C.c_void_p) if hd.size else None, hd.size)
     _lib.check(st, "mi_deflate_batch")
     return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]

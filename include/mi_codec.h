@@ -24,7 +24,7 @@
  * Decoders (*_decode_dev) synchronise `stream` before returning: MI_ERR_CORRUPT is decided on the device.  They take the
  * readable length of the stream and never read outside it, whatever an (untrusted) offset table says; every decode call
  * uses its own device status word, so decodes on different streams of one context do not interfere.
- * One exception: the batched inflate (mi_inflate_batch_dev, mi_inflate_batch_size_dev) and the BGZF range read
+ * One exception: the batched inflate (mi_inflate_batch_dev, mi_inflate_batch_size_dev, their _dict twins) and the BGZF range read
  * (mi_bgzf_read_ranges_dev) are asynchronous on `stream` under the encoders' contract above — their verdicts are per item and stay on the device, so nothing needs a host round trip: scratch is
  * the context workspace, the calls allocate or synchronise only while it grows, one call per context in flight at a time.
  */
@@ -597,6 +597,43 @@ mi_status mi_inflate_batch(mi_ctx *ctx, uint32_t container, uint64_t count, cons
                            void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status, uint32_t flags);
 
 /* ------------------------------------------------------------------------------------
+ * Batched inflate with a preset dictionary (zlib's FDICT: what inflateSetDictionary, or Python's
+ * zlib.decompressobj(wbits, zdict=...), reads): ONE dictionary per call, shared by all items, for
+ * the small unrelated buffers that have no history of their own to match against.
+ * d_dict: dict_bytes bytes on the device, read-only, no alignment required; it must stay as it is
+ * until the call has run.  Let E be its last min(dict_bytes, 32 768) bytes.  Everything above holds,
+ * with these differences:
+ *   raw    every item uses the dictionary.
+ *   zlib   an item whose header has FDICT = 1 has a 6-byte header — CMF, FLG and DICTID, four bytes
+ *          big-endian — and uses the dictionary if and only if DICTID is the Adler-32 of the WHOLE
+ *          dictionary (all dict_bytes); another DICTID is MI_ERR_CORRUPT for that item.  An item
+ *          with FDICT = 0 is decoded as without a dictionary.  The Adler-32 of the dictionary is
+ *          computed on the device, on `stream`, by the kernels of mi_adler32_dev: no host read.
+ *   gzip   has no dictionary field: with dict_bytes > 0 the call is MI_ERR_ARG.
+ * For an item that uses the dictionary a match may reach back to |E| bytes before the item's first
+ * byte — distance <= position + |E| and <= 32 768 — in the inflate, behind the capacity and in the
+ * size pass alike; it may start in E and run into the item's own output, and overlap itself across
+ * that seam.  One byte farther is MI_ERR_CORRUPT, as it is for an item that does not use the
+ * dictionary (FDICT = 0) one byte before its own first.  The trailer's Adler-32 covers the item's
+ * bytes only.  The items' waves read E alone; the Adler-32 reads all of the dictionary.
+ * dict_bytes == 0 (d_dict may then be NULL) is the call without a dictionary, verdict for verdict
+ * and byte for byte; a zlib item with FDICT is then MI_ERR_CORRUPT.  dict_bytes > 2^31 - 1, or
+ * d_dict == NULL with dict_bytes > 0, is MI_ERR_ARG.  The zlib form takes its checksum partials
+ * from the context's workspace (which grows, and synchronises, on first use only).
+ * mi_inflate_batch_dict: the host form; h_dict is host memory and travels up with the items.
+ * ------------------------------------------------------------------------------------ */
+mi_status mi_inflate_batch_dict_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in,
+                                    const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap,
+                                    uint64_t *d_out_bytes, uint32_t *d_status, uint32_t *d_failed, const uint8_t *d_dict,
+                                    uint64_t dict_bytes, uint32_t flags, void *stream);
+mi_status mi_inflate_batch_dict_size_dev(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *d_in,
+                                         const uint64_t *d_in_bytes, uint64_t *d_out_bytes, uint32_t *d_status, uint32_t *d_failed,
+                                         const uint8_t *d_dict, uint64_t dict_bytes, uint32_t flags, void *stream);
+mi_status mi_inflate_batch_dict(mi_ctx *ctx, uint32_t container, uint64_t count, const void *const *h_in, const uint64_t *h_in_bytes,
+                                void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status,
+                                const uint8_t *h_dict, uint64_t dict_bytes, uint32_t flags);
+
+/* ------------------------------------------------------------------------------------
  * Batched deflate: many independent buffers compressed in ONE call, each from its own address
  * and of its own size into its own buffer as a complete raw, zlib or gzip stream (one container
  * per call) — the twin of the batched inflate above, for Parquet / ORC pages, zarr / HDF5 chunks,
@@ -641,6 +678,45 @@ mi_status mi_deflate_batch_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t cont
 mi_status mi_deflate_batch(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
                            const void *const *h_in, const uint64_t *h_in_bytes,
                            void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status);
+
+/* ------------------------------------------------------------------------------------
+ * Batched deflate with a preset dictionary (zlib's FDICT: what deflateSetDictionary, or Python's
+ * zlib.compressobj(..., zdict=...), writes): ONE dictionary per call, shared by all items — the
+ * history a 700-byte item does not have.  The streams are standard: stock zlib inflates them with
+ * inflateSetDictionary / zlib.decompressobj(wbits, zdict=...), and so does
+ * mi_inflate_batch_dict_dev above.
+ * d_dict: dict_bytes bytes on the device, read-only, no alignment required.  An encoder may use
+ * any suffix of a dictionary; this one uses U, its last min(dict_bytes, 32 768, p->block / 2)
+ * bytes.  Everything of mi_deflate_batch_dev holds, with these differences:
+ *   blocks  item i's first record covers its first min(n_i, p->block - |U|) bytes — U and that head
+ *           are one block to the match finder, and the matches of the head may reach into U — and
+ *           its later records p->block bytes each, exactly the records of mi_deflate_batch_dev
+ *           for those bytes.  An item has at most one block more than without a dictionary:
+ *           mi_deflate_batch_dict_max_blocks (total / block + 2 count) bounds max_blocks, and
+ *           mi_deflate_batch_dict_bound_bytes an item's stream.
+ *   raw     no header: the caller tells the reader which dictionary it was.
+ *   zlib    the header is 78 BB and DICTID, the Adler-32 of the WHOLE dictionary (all dict_bytes)
+ *           big-endian: 6 bytes; then the records, 03 00 and the Adler-32 of the item's bytes.  An
+ *           empty item: header, 03 00, trailer.  DICTID is computed on the device, on `stream`.
+ *   gzip    has no dictionary field: with dict_bytes > 0 the call is MI_ERR_ARG, as zlib refuses it.
+ * dict_bytes == 0 (d_dict may then be NULL) is mi_deflate_batch_dev byte for byte; so is a block
+ * size below 2, which leaves no room for U.  dict_bytes > 2^31 - 1, or d_dict == NULL with
+ * dict_bytes > 0, is MI_ERR_ARG.  Verdicts, capacities (nothing written at or past one, the exact
+ * size needed reported), blocks beyond max_blocks and asynchrony are those of
+ * mi_deflate_batch_dev.  Workspace: one p->block-byte staging cell per block of a pipeline batch
+ * (MI_LZ_BATCH) and scratch set, whatever `count` is.
+ * mi_deflate_batch_dict: the host form; h_dict is host memory and travels up with the items.
+ * ------------------------------------------------------------------------------------ */
+uint64_t  mi_deflate_batch_dict_bound_bytes(uint64_t n_item, const mi_lz_params *p, uint32_t container, uint64_t dict_bytes);
+uint64_t  mi_deflate_batch_dict_max_blocks(uint64_t total_in_bytes, uint64_t count, const mi_lz_params *p, uint64_t dict_bytes);
+mi_status mi_deflate_batch_dict_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
+                                    const void *const *d_in, const uint64_t *d_in_bytes, uint64_t max_blocks,
+                                    void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                                    uint32_t *d_status, uint32_t *d_failed, const uint8_t *d_dict, uint64_t dict_bytes, void *stream);
+mi_status mi_deflate_batch_dict(mi_ctx *ctx, const mi_lz_params *p, uint32_t container, uint64_t count,
+                                const void *const *h_in, const uint64_t *h_in_bytes,
+                                void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status,
+                                const uint8_t *h_dict, uint64_t dict_bytes);
 
 /* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is

@@ -11,6 +11,14 @@ workspace and the encoders' fallback hint are per process), and prints its own J
 One JSON line.
 
     python scripts/bench_deflate_batch.py [--bytes 100000000] [--repeats 7]
+
+--dict: the preset-dictionary variant INSTEAD of the three cases.  The corpus behind its first 32 768 bytes (the dictionary)
+cut into --dict-item byte items (zlib container): the same items through mi_deflate_batch_dev and through
+mi_deflate_batch_dict_dev, alternating in one process, with the compressed bytes of both; and, with --parent-lib PATH (a
+libmi_codec.so built from the parent commit, loaded through MI_CODEC_LIB in a child of its own), mi_deflate_batch_dev of that
+library on the same items: `no_dict_over_parent` is the ratio of the medians, to be read against the two spreads.
+
+    python scripts/bench_deflate_batch.py --dict [--dict-item 700] [--repeats 3] [--parent-lib PATH]
 """
 import argparse
 import ctypes as C
@@ -66,6 +74,26 @@ class Batch:
         self.failed = torch.zeros(1, dtype=torch.int32, device=dev)
         self.max_blocks = sum((n + p.block - 1) // p.block for n in sizes)
 
+    def with_dict(self, d_dict):
+        """the same items behind a preset dictionary: capacities and the launch bound follow it"""
+        nd = d_dict.numel()
+        self.d_dict = d_dict
+        self.caps = [lz.deflate_batch_bound_bytes(n, self.p, self.c, nd) for n in self.sizes]
+        oo = np.concatenate([[0], np.cumsum([(c + 15) & ~15 for c in self.caps])])
+        self.out = torch.empty(int(oo[-1]) + 16, dtype=torch.uint8, device=self.ctx.device)
+        self.oo = oo
+        i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=self.ctx.device)
+        self.p_out, self.p_cap = i64([self.out.data_ptr() + int(a) for a in oo[:-1]]), i64(self.caps)
+        self.max_blocks = lz.deflate_batch_max_blocks(sum(self.sizes), self.count, self.p, dict_bytes=nd)
+        return self
+
+    def call_dict(self):
+        q = lambda t: C.c_void_p(t.data_ptr())
+        st = self.ctx.L.mi_deflate_batch_dict_dev(self.ctx.h, C.byref(self.p), self.c, self.count, q(self.p_in), q(self.p_nb), self.max_blocks,
+                                                  q(self.p_out), q(self.p_cap), q(self.nbytes), q(self.status), q(self.failed),
+                                                  q(self.d_dict), self.d_dict.numel(), self.ctx.stream_ptr())
+        assert st == 0, st
+
     def call(self):
         q = lambda t: C.c_void_p(t.data_ptr())
         st = self.ctx.L.mi_deflate_batch_dev(self.ctx.h, C.byref(self.p), self.c, self.count, q(self.p_in), q(self.p_nb), self.max_blocks,
@@ -101,7 +129,50 @@ def place(ctx, pieces, offs, total):
     return torch.from_numpy(h).to(ctx.device), h.tobytes()
 
 
+DICT_BYTES = 32768
+
+
+def dict_child(a):
+    """--dict in this process (under whatever MI_CODEC_LIB the parent set): prints its own JSON line"""
+    import zlib
+    ctx = lz.default_context()
+    p = lz.params("deflate")
+    x = synth.enwik_like(a.bytes, seed=a.seed).numpy().tobytes()
+    zd, body = x[:DICT_BYTES], x[DICT_BYTES:]
+    offs = list(range(0, len(body) - a.dict_item + 1, a.dict_item))
+    sizes = [a.dict_item] * len(offs)
+    n = sum(sizes)
+    d_x = torch.from_numpy(np.frombuffer(body, dtype=np.uint8).copy()).to(ctx.device)
+    res = dict(case=a.child, items=len(offs), item_bytes=a.dict_item, bytes=n, dict_bytes=len(zd), lib=os.environ.get("MI_CODEC_LIB", "tree"))
+
+    def out_bytes(b, zdict):
+        """a sanity check, not a test: every item MI_OK; the first, middle and last item read back by stock zlib"""
+        torch.cuda.synchronize()
+        assert int(b.failed[0]) == 0
+        nb = [int(v) for v in b.nbytes.cpu()]
+        for k in (0, b.count // 2, b.count - 1):
+            s = b.out[int(b.oo[k]):int(b.oo[k]) + nb[k]].cpu().numpy().tobytes()
+            d = zlib.decompressobj(15, zdict=zdict) if zdict else zlib.decompressobj(15)
+            assert d.decompress(s) + d.flush() == body[offs[k]:offs[k] + sizes[k]], k
+        return sum(nb)
+    plain = Batch(ctx, p, "zlib", d_x, offs, sizes)
+    plain.call()
+    res["no_dict_out_bytes"] = out_bytes(plain, None)
+    modes = [("no_dict", plain.call)]
+    if a.child == "dict":
+        d_dict = torch.from_numpy(np.frombuffer(zd, dtype=np.uint8).copy()).to(ctx.device)
+        withd = Batch(ctx, p, "zlib", d_x, offs, sizes).with_dict(d_dict)
+        withd.call_dict()
+        res["dict_out_bytes"] = out_bytes(withd, zd)
+        modes.append(("dict", withd.call_dict))
+    for m, t in timed(modes, a.repeats).items():
+        res[m] = summary(t, n)
+    print(json.dumps(res))
+
+
 def child(a):
+    if a.child in ("dict", "dict-parent"):
+        return dict_child(a)
     ctx = lz.default_context()
     p = lz.params("deflate")
     if a.child == "skewed":
@@ -154,11 +225,26 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--skew-small", type=int, default=10_000)
     ap.add_argument("--skew-big", type=int, default=4)
-    ap.add_argument("--child", choices=("uniform", "aligned", "skewed"))
+    ap.add_argument("--child", choices=("uniform", "aligned", "skewed", "dict", "dict-parent"))
+    ap.add_argument("--dict", action="store_true")
+    ap.add_argument("--dict-item", type=int, default=700)
+    ap.add_argument("--parent-lib", default=None)
     a = ap.parse_args()
     if a.child:
         return child(a)
     res = dict(device=torch.cuda.get_device_name(0), bytes=a.bytes, repeats=a.repeats)
+    if a.dict:
+        for case in ("dict", "dict-parent") if a.parent_lib else ("dict",):
+            env = dict(os.environ, MI_CODEC_LIB=os.path.abspath(a.parent_lib)) if case == "dict-parent" else dict(os.environ)
+            c = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case, "--bytes", str(a.bytes), "--repeats", str(a.repeats),
+                                "--seed", str(a.seed), "--dict-item", str(a.dict_item)], capture_output=True, text=True, timeout=900, env=env)
+            assert c.returncode == 0, c.stderr[-2000:]
+            res[case.replace("-", "_")] = json.loads(c.stdout.strip().splitlines()[-1])
+        res["dict_over_no_dict"] = round(res["dict"]["dict"]["ms_median"] / res["dict"]["no_dict"]["ms_median"], 4)
+        if a.parent_lib:
+            res["no_dict_over_parent"] = round(res["dict"]["no_dict"]["ms_median"] / res["dict_parent"]["no_dict"]["ms_median"], 4)
+        print(json.dumps(res))
+        return
     for case in ("uniform", "aligned", "skewed"):
         c = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case, "--bytes", str(a.bytes), "--repeats", str(a.repeats),
                             "--seed", str(a.seed), "--skew-small", str(a.skew_small), "--skew-big", str(a.skew_big)],

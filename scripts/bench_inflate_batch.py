@@ -11,6 +11,15 @@ alternating runs in one process, with min and max so that the run-to-run spread 
 One JSON line.
 
     python scripts/bench_inflate_batch.py [--bytes 100000000] [--repeats 7]
+
+--dict: the preset-dictionary variant INSTEAD of the three cases.  The corpus behind its first 32 768 bytes (the dictionary)
+cut into --dict-item byte items, each compressed by stock zlib (level 6, zlib container) without and with zdict=: the
+former through mi_inflate_batch_dev, the latter through mi_inflate_batch_dict_dev, alternating in one process; and, with
+--parent-lib PATH (a libmi_codec.so built from the parent commit, loaded through MI_CODEC_LIB in a child of its own),
+mi_inflate_batch_dev of that library on the same items: `no_dict_over_parent` is the ratio of the medians, to be read against
+the two spreads.
+
+    python scripts/bench_inflate_batch.py --dict [--dict-item 700] [--repeats 3] [--parent-lib PATH]
 """
 import argparse
 import ctypes as C
@@ -84,6 +93,13 @@ class Batch:
                                              p(self.nbytes), p(self.status), p(self.failed), flags, self.ctx.stream_ptr())
         assert st == 0, st
 
+    def call_dict(self, d_dict):
+        p = lambda t: C.c_void_p(t.data_ptr())
+        st = self.ctx.L.mi_inflate_batch_dict_dev(self.ctx.h, self.c, self.count, p(self.p_in), p(self.p_nb), p(self.p_out), p(self.p_cap),
+                                                  p(self.nbytes), p(self.status), p(self.failed), p(d_dict), d_dict.numel(), 0,
+                                                  self.ctx.stream_ptr())
+        assert st == 0, st
+
     def sizes(self):
         p = lambda t: C.c_void_p(t.data_ptr())
         st = self.ctx.L.mi_inflate_batch_size_dev(self.ctx.h, self.c, self.count, p(self.p_in), p(self.p_nb), p(self.nbytes), p(self.status),
@@ -133,6 +149,43 @@ def skewed_child(a):
                           uniform_items=len(pieces), order=os.environ.get("MI_INFLATE_BATCH_ORDER", "unset"))))
 
 
+DICT_BYTES = 32768
+
+
+def dict_child(a):
+    """--dict in this process (under whatever MI_CODEC_LIB the parent set): prints its own JSON line"""
+    ctx = lz.default_context()
+    x = synth.enwik_like(a.bytes, seed=a.seed).numpy().tobytes()
+    zd, body = x[:DICT_BYTES], x[DICT_BYTES:]
+    pieces = [body[i:i + a.dict_item] for i in range(0, len(body) - a.dict_item + 1, a.dict_item)]
+    n = sum(len(p) for p in pieces)
+    want = torch.from_numpy(np.frombuffer(b"".join(pieces), dtype=np.uint8).copy()).to(ctx.device)
+    res = dict(case=a.dict_child, items=len(pieces), item_bytes=a.dict_item, bytes=n, dict_bytes=len(zd), lib=os.environ.get("MI_CODEC_LIB", "tree"))
+
+    def stock(p, zdict):
+        c = zlib.compressobj(6, zlib.DEFLATED, 15, 8, zlib.Z_DEFAULT_STRATEGY, zdict) if zdict else zlib.compressobj(6, zlib.DEFLATED, 15)
+        return c.compress(p) + c.flush()
+    items = [stock(p, None) for p in pieces]
+    res["no_dict_in_bytes"] = sum(len(i) for i in items)
+    buf, ptrs, sizes = packed(ctx, items)
+    plain = Batch(ctx, "zlib", ptrs, sizes, [len(p) for p in pieces])
+    plain.call()
+    plain.check(want)
+    modes = [("no_dict", plain.call)]
+    if a.dict_child == "dict":
+        d_dict = torch.from_numpy(np.frombuffer(zd, dtype=np.uint8).copy()).to(ctx.device)
+        ditems = [stock(p, zd) for p in pieces]
+        res["dict_in_bytes"] = sum(len(i) for i in ditems)
+        dbuf, dptrs, dsizes = packed(ctx, ditems)
+        withd = Batch(ctx, "zlib", dptrs, dsizes, [len(p) for p in pieces])
+        withd.call_dict(d_dict)
+        withd.check(want)
+        modes.append(("dict", lambda: withd.call_dict(d_dict)))
+    for m, t in timed(modes, a.repeats).items():
+        res[m] = summary(t, n)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bytes", type=int, default=100_000_000)
@@ -142,9 +195,28 @@ def main():
     ap.add_argument("--skew-big", type=int, default=4)
     ap.add_argument("--child-uniform", type=int, default=64_000_000)
     ap.add_argument("--skewed-child", action="store_true")
+    ap.add_argument("--dict", action="store_true")
+    ap.add_argument("--dict-item", type=int, default=700)
+    ap.add_argument("--dict-child", choices=("dict", "dict-parent"))
+    ap.add_argument("--parent-lib", default=None)
     a = ap.parse_args()
     if a.skewed_child:
         return skewed_child(a)
+    if a.dict_child:
+        return dict_child(a)
+    if a.dict:
+        res = dict(device=torch.cuda.get_device_name(0), bytes=a.bytes, repeats=a.repeats)
+        for case in ("dict", "dict-parent") if a.parent_lib else ("dict",):
+            env = dict(os.environ, MI_CODEC_LIB=os.path.abspath(a.parent_lib)) if case == "dict-parent" else dict(os.environ)
+            c = subprocess.run([sys.executable, os.path.abspath(__file__), "--dict-child", case, "--bytes", str(a.bytes), "--repeats", str(a.repeats),
+                                "--seed", str(a.seed), "--dict-item", str(a.dict_item)], capture_output=True, text=True, timeout=900, env=env)
+            assert c.returncode == 0, c.stderr[-2000:]
+            res[case.replace("-", "_")] = json.loads(c.stdout.strip().splitlines()[-1])
+        res["dict_over_no_dict"] = round(res["dict"]["dict"]["ms_median"] / res["dict"]["no_dict"]["ms_median"], 4)
+        if a.parent_lib:
+            res["no_dict_over_parent"] = round(res["dict"]["no_dict"]["ms_median"] / res["dict_parent"]["no_dict"]["ms_median"], 4)
+        print(json.dumps(res))
+        return
     dev = torch.device("cuda", 0)
     ctx = lz.default_context()
     x = synth.enwik_like(a.bytes, seed=a.seed, device=dev)
