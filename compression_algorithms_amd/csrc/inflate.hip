@@ -158,8 +158,7 @@ extern "C" mi_status mi_inflate_dev(mi_ctx *ctx, uint32_t container, uint32_t bl
         mi_prof_scope pr(ctx, "k_inflate", s, n);
         // a 4 KiB ring (lz_decode.h): far matches read the output buffer.  Few segments cannot fill the CUs anyway and get
         // the whole 32 KiB window in LDS.
-        const char *e = getenv("MI_LZ_DECODE_RING");
-        const uint32_t want = e ? (uint32_t)atoi(e) : (nseg < 1024u ? 32768u : 4096u);
+        const uint32_t want = lz_decode_ring_want(nseg, 32768u, 4096u);
         if (want <= 4096u) hipLaunchKernelGGL(k_inflate<4096u>, dim3((unsigned)nseg), dim3(64), 0, s, d_stream, stream_bytes, d_seg_bits, block, nseg, d_out, n, status, err, (uint32_t *)nullptr);
         else hipLaunchKernelGGL(k_inflate<32768u>, dim3((unsigned)nseg), dim3(64), 0, s, d_stream, stream_bytes, d_seg_bits, block, nseg, d_out, n, status, err, (uint32_t *)nullptr);
         if (hipGetLastError() != hipSuccess) return MI_ERR_HIP;

@@ -219,8 +219,7 @@ static mi_status batch_launch(mi_ctx *ctx, uint32_t container, uint64_t count, c
     {
         mi_prof_scope pr(ctx, count_only ? "k_inflate_batch_size" : "k_inflate_batch", s, 0);
         // the ring: as mi_inflate_dev — few items cannot fill the CUs anyway and get the whole 32 KiB window in LDS
-        const char *r = getenv("MI_LZ_DECODE_RING");
-        const uint32_t want = r ? (uint32_t)atoi(r) : (cnt < 1024u ? 32768u : 4096u);
+        const uint32_t want = lz_decode_ring_want(cnt, 32768u, 4096u);
         if (dict) {
             const InfDict<true> dd{d_dict + dict_bytes, (uint32_t)(dict_bytes < 32768u ? dict_bytes : 32768u), d_adler};
             if (count_only) hipLaunchKernelGGL((k_inflate_batch<4096u, true, true>), dim3(cnt), dim3(64), 0, s, b, dd);

@@ -12,36 +12,38 @@ size_t    huff_ws_bytes(uint64_t n);
 
 // ---- lz_find.hip: parameters, workspace and the stages of the match finder
 mi_status lz_check_params(const mi_lz_params *p);
-void      lz_carve(mi_carver &cv, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2);            // one scratch set; sets are multiples of 4096
-uint32_t  lz_batch_blocks(mi_ctx *ctx, uint64_t nblocks);
-bool      lz_use_v2();
+// (what a call decides before it queues anything — LzSwitches, LzHint, LzPlan — is lz_plan.h: read once per call at the entry point)
+void      lz_carve(mi_carver &cv, uint32_t nb, bool debug, LzScratch *sc, Lz2Scratch *sc2);   // one scratch set; sets are multiples of 4096
+LzHint    lz_hint_read(const mi_ctx *ctx);
 mi_status lz_find_stage_a(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                           const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s, hipStream_t sf, hipEvent_t ev_part, hipEvent_t ev_fb,
-                          hipEvent_t ev_wide);
-mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which);
+                          hipEvent_t ev_wide, const LzPlan &plan);
+mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which, const LzPlan &plan);
 
 // ---- lz2_partition.hip, lz2_find.hip: the LDS-resident finder
 void      lz2_launch_partition(const uint8_t *d_in, uint64_t n, const LzP &P, const Lz2Scratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
-void      lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc);
+void      lz2_carve(mi_carver &cv, uint32_t nb, bool debug, Lz2Scratch *sc);                  // debug: the phase counters are carved
+void      lz2_set_switches(Lz2Scratch *sc, const LzSwitches &sw);                             // wave_min, prefix, stop_phase of a carved set
 mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                               const Lz2Scratch &sc, hipStream_t s);
 mi_status lz2_stage_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                          const Lz2Scratch &sc, hipStream_t s);
 mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                              const Lz2Scratch &sc, hipStream_t s, bool aside);
-mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which);
+                              const Lz2Scratch &sc, hipStream_t s, bool aside, const LzPlan &plan);
+mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which, const LzPlan &plan);
 void      lz2_launch_scatter(const Lz2Scratch &sc, uint16_t *cand_by_pos, uint32_t nb, hipStream_t s);
 
 // ---- lzw.hip: the lz77 flavour on blocks above 64 KiB
 mi_status lzw_reserve(mi_ctx *ctx, uint32_t *nb, uint32_t block, LzwScratch *sc, uint64_t **base_bits);   // measures, halves *nb on MI_ERR_NOMEM, places
 uint32_t  lzw_batch_blocks(mi_ctx *ctx, uint64_t nblocks, uint32_t block);
-mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s);
+mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s,
+                          const LzSwitches &sw);
 void      lzw_launch_parse_emit(const uint8_t *d_in, uint64_t n, const LzP &P, const LzwScratch &sc, uint64_t block0, uint32_t nb, hipStream_t s);
 
 // ---- lzs.hip: the time-sliced LDS-resident finder for those blocks
-bool      lzs_applicable(const LzP &P);
+bool      lzs_applicable(const LzP &P, bool sliced);                       // sliced: MI_LZW_SLICED
 mi_status lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                   const LzwScratch &ws, hipStream_t s, uint32_t *flagged, const uint32_t **flag_list);
+                   const LzwScratch &ws, hipStream_t s, uint32_t *flagged, const uint32_t **flag_list, const LzSwitches &sw);
 
 // ---- lz_decode.hip; lz_emit.hip: block sizes -> offsets in place and the published table, the block decoder without its closing
 // status read (host_api.hip launches one per chunk)

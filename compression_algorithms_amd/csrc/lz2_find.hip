@@ -1376,7 +1376,7 @@ static uint32_t lz2_class_cap(uint32_t c)
     return LZ_MAX_BLOCK / lo[c] + 8;
 }
 
-void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
+void lz2_carve(mi_carver &cv, uint32_t nb, bool debug, Lz2Scratch *sc)
 {
     sc->partmap = cv.take<uint8_t>((size_t)nb * LZ_MAX_BLOCK);
     sc->plist = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
@@ -1395,24 +1395,21 @@ void lz2_carve(mi_carver &cv, uint32_t nb, Lz2Scratch *sc)
     sc->work = cv.take<uint64_t>((size_t)nb * LZ2_MAXPARTS);
     sc->work_slots = nb * LZ2_MAXPARTS;
     sc->lane_list = cv.take<uint4>((size_t)nb * lz2_class_cap(7));
-    sc->dbg = getenv("MI_LZ_DEBUG") ? cv.take<uint64_t>(64) : nullptr;
+    sc->dbg = debug ? cv.take<uint64_t>(64) : nullptr;       // the phase counters (MI_LZ_DEBUG)
+}
+
+// what the kernels read of the switches, into a carved set (its dbg is the carve's)
+void lz2_set_switches(Lz2Scratch *sc, const LzSwitches &sw)
+{
     // bits 16..: the row replay's switch (MI_LZ_ROWS, lz2_stage_b): with it the wave classes are three (128..255 apart)
-    { const char *e = getenv("MI_LZ_ROWS"); const uint32_t rows = e ? (uint32_t)atoi(e) : 1u; sc->wave_min = LZ2_WAVE | ((rows ? 1u : 0u) << 16); }
+    sc->wave_min = LZ2_WAVE | ((sw.rows ? 1u : 0u) << 16);
     // MI_LZ_PREFIX=0: no k_lz2_prefix, every replay starts at entry 0 (A/B and the parity test, nothing else)
-    { const char *e = getenv("MI_LZ_PREFIX"); sc->prefix = e ? (atoi(e) ? 1u : 0u) : 1u; }
+    sc->prefix = sw.prefix ? 1u : 0u;
 #ifdef MI_MEASURE
-    sc->stop_phase = getenv("MI_LZ_STOP_PHASE") ? (uint32_t)atoi(getenv("MI_LZ_STOP_PHASE")) : 0u;
+    sc->stop_phase = sw.stop_phase;
 #else
     sc->stop_phase = 0u;
 #endif
-}
-
-static uint32_t lz2_env_u32(const char *name, uint32_t dflt)
-{
-    const char *e = getenv(name);
-    if (!e) return dflt;
-    const long v = atol(e);
-    return v >= 0 ? (uint32_t)v : dflt;
 }
 
 // phase cycle counters of the last LZ call of this context (MI_LZ_DEBUG=1; a development hook, not in the public header)
@@ -1476,14 +1473,13 @@ mi_status lz2_stage_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_
 // for that behind the parse kernel of the batch before, on the one chain the pipeline is bound by (kernel timeline, round 4:
 // partition 3.7 + find 4.45 + this 1.0 ms of a 9.3 ms batch period)
 mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                              const Lz2Scratch &sc, hipStream_t s, bool aside)
+                              const Lz2Scratch &sc, hipStream_t s, bool aside, const LzPlan &plan)
 {
     // on the side stream this launch is normally empty and merely waits for its LDS behind the other stages (6 ms of "duration"
     // per batch in rocprofv3): timing it would report that wait as the pipeline's dominant kernel (as for the fallback chain,
     // lz_find_batch); MI_LZ_PROF_FALLBACK=1 times it (inputs with wide parts: scripts/adv_profile.py)
-    static const bool prof_fb = getenv("MI_LZ_PROF_FALLBACK") != nullptr;
     const int saved_prof = ctx->profiling;
-    if (aside && !prof_fb) ctx->profiling = 0;
+    if (aside && !plan.sw.prof_fallback) ctx->profiling = 0;
     {
         mi_prof_scope p(ctx, "k_lz2_find_wide", s, (uint64_t)nb * P.block);
         if (P.flags & LZP_DESC) hipLaunchKernelGGL(k_lz2_find_wide<true>, dim3(256), dim3(LZ2_THREADS), 0, s, d_in, n, P, sc, block0, lz2_find_grid(P, nb));
@@ -1496,7 +1492,7 @@ mi_status lz2_stage_find_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, ui
 
 // stage B: replay of the exported clusters (almost no LDS: runs beside the next batch's stage A)
 // which: 4 = the lane replays (8..127-entry clusters), 2 = the wave / row replays; 7 = both on `s`
-mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which)
+mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc, hipStream_t s, int which, const LzPlan &plan)
 {
     // Replay grids cover the worst case and the kernels stride, so any grid is correct.  Measured (round 2, same box):
     // persistent grids sized by LDS (16 / 12 / 7 / 5 / 16 waves per CU) left the lane classes unchanged and made the wave
@@ -1507,8 +1503,7 @@ mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &
     // the lane classes: ordering pass + ONE launch of k_lz2_lanes (one-batch calls: on the stream of `which & 4`).
     // MI_LZ_LANES_KIB: LDS per wave of k_lz2_lanes (A/B).
     if (which & 4) {
-        static const uint32_t kib_env = lz2_env_u32("MI_LZ_LANES_KIB", 8);
-        const uint32_t kib = kib_env < 1u ? 1u : kib_env > 32u ? 32u : kib_env, budget_dw = kib * 256u;    // >= lz2_lane_region(127)
+        const uint32_t budget_dw = plan.sw.lanes_kib * 256u;                     // 1..32 KiB: >= lz2_lane_region(127)
         const uint64_t worst = (uint64_t)nb * lz2_class_cap(7);                  // lane-class clusters of the batch, at most
         const uint32_t og = (uint32_t)((worst + 255u) / 256u < (uint64_t)ncu * 4u ? (worst + 255u) / 256u : (uint64_t)ncu * 4u);
         { mi_prof_scope p(ctx, "k_lz2_lane_order", s, (uint64_t)nb * P.block);
@@ -1530,24 +1525,21 @@ mi_status lz2_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &
       // the 512..1024-entry class first and alone on the wave replay (6 KiB of LDS per wave), then the 128..511-entry clusters: on the
       // row replay (below), or — MI_LZ_ROWS=0 — on the wave replay with 3 KiB per wave (MI_LZ_BIG_SPLIT=0: one launch for both wave
       // classes, A/B)
-      static const bool split = !(getenv("MI_LZ_BIG_SPLIT") && getenv("MI_LZ_BIG_SPLIT")[0] == '0');
       // row replay (four clusters per wave, off a cursor) of the 128..511-entry clusters, the 256..511 ones first (MI_LZ_ROWS=0: the
       // wave replay for everything, A/B); k_lz2_big then takes what the rows leave (the cluster that covers bucket 0 / T) with
       // small grids that stride over the descriptors
-      const uint32_t rows = sc.wave_min >> 16;
-      static const uint32_t rows_waves = lz2_env_u32("MI_LZ_ROWS_WAVES", 9);
-      if (rows >= 1 && split && (sc.wave_min & 0xFFFFu) == LZ2_WAVE) {
+      if (plan.b_shape == LZ_B_ROWS_SPLIT) {
           hipLaunchKernelGGL((k_lz2_big<LZ2_BIG_SMALL, 1>), dim3(grid_of((uint64_t)nb * lz2_class_cap(4))), dim3(64), 0, s, P, sc, 3);
-          hipLaunchKernelGGL((k_lz2_rows<16>), dim3(ncu * rows_waves), dim3(64), 0, s, P, sc, 5, 3, 9);
+          hipLaunchKernelGGL((k_lz2_rows<16>), dim3(ncu * plan.sw.rows_waves), dim3(64), 0, s, P, sc, 5, 3, 9);
           hipLaunchKernelGGL((k_lz2_big<512, 1>), dim3(ncu * 4u), dim3(64), 0, s, P, sc, 2);
           hipLaunchKernelGGL((k_lz2_big<256, 1>), dim3(ncu * 4u), dim3(64), 0, s, P, sc, 4);
-      } else if (split && (sc.wave_min & 0xFFFFu) == LZ2_WAVE) {
+      } else if (plan.b_shape == LZ_B_SPLIT) {
           hipLaunchKernelGGL((k_lz2_big<LZ2_BIG_SMALL, 1>), dim3(grid_of((uint64_t)nb * lz2_class_cap(4))), dim3(64), 0, s, P, sc, 3);
           hipLaunchKernelGGL((k_lz2_big<512, 1>), dim3(grid_of((uint64_t)nb * lz2_class_cap(5))), dim3(64), 0, s, P, sc, 2);
       } else {
           hipLaunchKernelGGL((k_lz2_big<LZ2_BIG_SMALL, 1>), dim3(grid_of((uint64_t)nb * (lz2_class_cap(4) + lz2_class_cap(5)))), dim3(64), 0, s, P, sc, 0);
           // (with the row replay's three classes but MI_LZ_BIG_SPLIT=0: the 128..255 class has its own list)
-          if (rows) hipLaunchKernelGGL((k_lz2_big<256, 1>), dim3(grid_of((uint64_t)nb * lz2_class_cap(3))), dim3(64), 0, s, P, sc, 4);
+          if (plan.sw.rows) hipLaunchKernelGGL((k_lz2_big<256, 1>), dim3(grid_of((uint64_t)nb * lz2_class_cap(3))), dim3(64), 0, s, P, sc, 4);
       } }
     { mi_prof_scope p(ctx, "k_lz2_dom", s, (uint64_t)nb * P.block);
       // clusters above 1024 entries that one word dominates (none in text: an empty launch of 13 KiB workgroups); what it leaves

@@ -9,6 +9,7 @@
 // dense occupancy bitmap held in LDS.  DESIGN.md has the argument and the measurements.
 #pragma once
 #include "common.h"
+#include "lz_plan.h"                 // LZ_FB_GRID; the switches, the hint and the plan of an encoder call
 #include <type_traits>
 
 #define LZ_MAX_BLOCK   65536u

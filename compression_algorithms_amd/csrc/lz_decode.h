@@ -8,6 +8,16 @@
 // huffman.c:330-364 (tree walk per bit).
 #pragma once
 #include "lz_common.h"
+#include <stdlib.h>
+
+// The ring a decoder launch asks for, in bytes: MI_LZ_DECODE_RING forces a size (A/B runs); else `few` while the call has fewer
+// than 1 024 units (blocks, segments, items: they cannot fill the CUs, more waves are no use), `many` from there on.  Each
+// decoder maps the answer onto its own ladder of instantiations.
+static inline uint32_t lz_decode_ring_want(uint64_t units, uint32_t few, uint32_t many)
+{
+    const char *e = getenv("MI_LZ_DECODE_RING");
+    return e ? (uint32_t)atoi(e) : (units < 1024u ? few : many);
+}
 
 // A window of 64 stream dwords in registers, the next 64 already in flight.  `first` is a dword-aligned pointer, `nw`
 // the number of dwords that may be read (everything past it reads as zero: no access outside the block's own range).

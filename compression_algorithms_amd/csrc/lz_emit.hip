@@ -548,7 +548,7 @@ __device__ __forceinline__ uint32_t stream_bits(const uint8_t *s, uint64_t nbyte
 
 // blocks above 64 KiB (lz77 flavour): the HBM-resident finder of lzw.hip, one stream, batches sized by workspace
 static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
-                                uint64_t *d_block_bits, uint64_t nblocks, hipStream_t s)
+                                uint64_t *d_block_bits, uint64_t nblocks, hipStream_t s, const LzSwitches &sw)
 {
     uint32_t nbw = lzw_batch_blocks(ctx, nblocks, P.block);
     LzwScratch ws; uint64_t *base_bits_w;
@@ -558,7 +558,7 @@ static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, 
     if (nblocks == 0) { MI_HIP(ctx, hipMemsetAsync(d_block_bits, 0, 8, s)); return MI_OK; }
     for (uint64_t b0 = 0; b0 < nblocks; b0 += nbw) {
         const uint32_t nb = (uint32_t)((nblocks - b0) < nbw ? (nblocks - b0) : nbw);
-        st = lzw_or_lzs_find(ctx, P, d_in, n, b0, nb, ws, s);
+        st = lzw_or_lzs_find(ctx, P, d_in, n, b0, nb, ws, s, sw);
         if (st) return st;
         { mi_prof_scope pr(ctx, "k_lzw_parse_emit", s, (uint64_t)nb * P.block);
           lzw_launch_parse_emit(d_in, n, P, ws, b0, nb, s); }
@@ -578,9 +578,9 @@ static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, 
 struct LzWs { LzScratch sc[MI_SETS]; Lz2Scratch sc2[MI_SETS]; uint64_t *base_bits; uint32_t *trec; void *zws; uint8_t *stage[MI_SETS]; };
 
 // stage_bytes: a batch with a preset dictionary stages its items' first blocks behind the dictionary's tail, one cell per block slot of a set
-static void lz_carve_all(mi_carver &cv, uint32_t nb, int nsets, size_t trec_words, size_t z_bytes, size_t stage_bytes, LzWs *w)
+static void lz_carve_all(mi_carver &cv, uint32_t nb, int nsets, bool debug, size_t trec_words, size_t z_bytes, size_t stage_bytes, LzWs *w)
 {
-    for (int k = 0; k < nsets; ++k) lz_carve(cv, nb, &w->sc[k], &w->sc2[k]);
+    for (int k = 0; k < nsets; ++k) lz_carve(cv, nb, debug, &w->sc[k], &w->sc2[k]);
     for (int k = 0; k < MI_SETS; ++k) w->stage[k] = k < nsets && stage_bytes ? cv.take<uint8_t>(stage_bytes) : nullptr;
     w->base_bits = reinterpret_cast<uint64_t *>(cv.take<uint8_t>(8192));
     w->trec = trec_words ? cv.take<uint32_t>(trec_words) : nullptr;
@@ -589,51 +589,33 @@ static void lz_carve_all(mi_carver &cv, uint32_t nb, int nsets, size_t trec_word
 
 // The stream of the fallback chains of the ODD batches of a pipelined call (the even ones' is ctx->fb); creates or releases
 // ctx->fb2.  `sb`: stage B's stream.
-static hipStream_t lz_odd_fallback_stream(mi_ctx *ctx, bool overlap, hipStream_t sb)
+static hipStream_t lz_odd_fallback_stream(mi_ctx *ctx, const LzPlan &plan, hipStream_t sb)
 {
-    // The fallback chains of consecutive batches go to two streams WHEN the input lives in the fallback: their kernels are long
-    // serial chains on few workgroups and overlap well — pages 1.72 -> 2.16, runs 1.65 -> 2.77 GB/s on 10^8 B.  On text a second
-    // stream costs 7 % even idle (20.4 -> 19.1 GB/s, whatever GPU_MAX_HW_QUEUES says), so it exists only while the hint says so.
-    // The hint (ctx->h_order[1]) is the fallback count of the last batch the GPU has FINISHED — every batch of a call is queued
-    // before the first one runs, so in practice it is what an EARLIER call left: a first call on non-text input runs on one
-    // fallback stream and small grids, a text call right after such input still carries the second stream (bench.py reports the
-    // adversarial families warm AND cold).  Decided once per call; the stream is created here and released here — when a later
-    // call finds the hint low and the stream idle (hipStreamQuery: no host wait) — or with the context, never inside the loop
-    // (stream create/destroy per batch, skipped on early returns, may block in hipStreamDestroy).
-    const uint32_t fb_hint = (overlap && ctx->h_order) ? __atomic_load_n(ctx->h_order + 1, __ATOMIC_RELAXED) : 0u;
-    const bool fb_busy = fb_hint > 8u;                                                                             // (text: 0)
-    // When MOST blocks of a batch fall back (zeros, binary pages) stage B has next to nothing to do: the chains of the odd batches
-    // then go to ITS stream and no fifth stream is made at all — every stream beyond the four of the pipeline costs all of them
-    // (the process has four hardware queues: pages 33.2 -> 29.5 ms, zeros 12.2 -> 8.4 ms per 10^8 B against fb2).  Where stage B has
-    // real work beside the fallback (the "runs" family: 17 % of the blocks fall back, the rest export wide clusters) a chain in front
-    // of it costs more than the fifth stream (22.5 -> 27.2 ms): there fb2 stays.  MI_LZ_FB2_SIDE=0 / 1 forces either (A/B).
-    static const char *fb2_env = getenv("MI_LZ_FB2_SIDE");
-    const uint32_t fb_of = (overlap && ctx->h_order) ? __atomic_load_n(ctx->h_order + 2, __ATOMIC_RELAXED) : 0u;    // blocks of the batch the hint is from
-    const bool fb2_side = fb_busy && (fb2_env ? fb2_env[0] == '1' : fb_hint * 2u >= fb_of);
-    if (fb_busy && !ctx->fb2 && !fb2_side) {
+    // where the chains go and whether the second stream should exist: lz_plan.h, from the call's one read of the hint
+    if (plan.want_fb2 && !ctx->fb2) {
         int lo_ = 0, hi_ = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo_, &hi_);
         if (hipStreamCreateWithPriority(&ctx->fb2, hipStreamNonBlocking, lo_) != hipSuccess) { (void)hipGetLastError(); ctx->fb2 = nullptr; }
-    } else if ((!fb_busy || fb2_side) && ctx->fb2) {
+    } else if (!plan.want_fb2 && ctx->fb2) {
         if (hipStreamQuery(ctx->fb2) == hipSuccess) { (void)hipStreamDestroy(ctx->fb2); ctx->fb2 = nullptr; }
         else (void)hipGetLastError();                     // still draining an earlier call's chains: try again next time
     }
-    return fb2_side ? sb : (fb_busy && ctx->fb2) ? ctx->fb2 : ctx->fb;
+    return plan.odd_chain == LZ_ODD_STAGE_B ? sb : (plan.odd_chain == LZ_ODD_FB2 && ctx->fb2) ? ctx->fb2 : ctx->fb;
 }
 
 // Stage B of a call of ONE batch (no pipeline: the side and fallback streams are idle): the lane replays run BESIDE the wave / row
 // replays, on the side stream — the two groups are independent, each is a chain of launches with tails, and what follows needs
 // both; the (normally empty) fallback chain and the wide finder have left the partition -> find chain for the fallback stream as
 // in the pipeline (MI_LZ_B_SPLIT=0: one chain on one stream, A/B)
-static mi_status lz_stage_b_solo(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s)
+static mi_status lz_stage_b_solo(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, const LzPlan &plan)
 {
     MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_wide[0], 0));                                             // the wide parts' exports
     MI_HIP(ctx, hipEventRecord(ctx->ev_find[0], s));
     MI_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_find[0], 0));
-    mi_status st = lz_find_stage_b(ctx, P, nb, sc2, ctx->side, 4);
+    mi_status st = lz_find_stage_b(ctx, P, nb, sc2, ctx->side, 4, plan);
     if (st) return st;
     MI_HIP(ctx, hipEventRecord(ctx->ev_replay[0], ctx->side));
-    st = lz_find_stage_b(ctx, P, nb, sc2, s, 2);
+    st = lz_find_stage_b(ctx, P, nb, sc2, s, 2, plan);
     MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_replay[0], 0));
     MI_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_fb[0], 0));                                               // the fallback blocks' candidates
     return st;
@@ -654,23 +636,23 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
     LzP P = lz_params_of(ctx, p);
     if (items) P.flags |= LZP_DESC;
     const uint64_t nblocks = items ? c.batch->max_blocks : (n + P.block - 1) / P.block;
+    // how this call runs: the switches and the hint, read here and nowhere below (lz_plan.h)
+    const LzSwitches sw = lz_switches_read();
+    const LzHint hint = lz_hint_read(ctx);
     if (P.block > LZ_MAX_BLOCK)
-        return c.form == LZ_TOKENS ? lz_encode_wide(ctx, P, d_in, n, d_out, cap_bytes, d_block_bits, nblocks, s) : MI_ERR_ARG;
-    const uint32_t nbmax = lz_batch_blocks(ctx, nblocks);
-    // three stages on three streams, MI_SETS scratch sets in rotation:
-    //   `s`          partition + find of batch i+2          (LDS heavy: one / three workgroups per CU)
-    //   ctx->side    replay of the exported clusters of i+1 (almost no LDS: runs beside the find)
-    //   ctx->parse   parse / emit / concatenate of batch i  (one 150 KiB workgroup per CU; the stream has raised priority)
-    // plus ctx->fb for the normally empty fallback chain.  Fork/join with events only: no host synchronisation.
-    const bool overlap = nblocks > nbmax && !getenv("MI_LZ_NO_OVERLAP");
-    const int nsets = overlap ? MI_SETS : 1;
+        return c.form == LZ_TOKENS ? lz_encode_wide(ctx, P, d_in, n, d_out, cap_bytes, d_block_bits, nblocks, s, sw) : MI_ERR_ARG;
+    const LzPlan plan = lz_plan(nblocks, (uint32_t)ctx->num_cu, hint, sw);
+    const uint32_t nbmax = plan.nbmax;
+    const bool overlap = plan.overlap, solo = plan.solo;
+    const int nsets = plan.nsets, skip = plan.skip, v2 = sw.v2 ? 1 : 0;
     const size_t trec_words = c.form == LZ_TOKENS ? 0 : (size_t)nbmax * LZ_MAX_BLOCK * nsets;
     const size_t z_bytes = items ? dfb_ws_bytes(*c.batch) : (c.form == LZ_Z || c.form == LZ_BGZF) ? defz_ws_bytes() : 0;
     const bool dict = items && c.batch->ulen != 0;                 // a preset dictionary: items' first blocks are staged behind its tail
     const size_t stage_bytes = dict ? dfb_stage_bytes(*c.batch, nbmax, P.block) : 0;
     LzWs t;
-    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve_all(cv, nbmax, nsets, trec_words, z_bytes, stage_bytes, &t); });
+    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve_all(cv, nbmax, nsets, sw.debug, trec_words, z_bytes, stage_bytes, &t); });
     if (st) return st;
+    for (int k = 0; k < nsets; ++k) lz2_set_switches(&t.sc2[k], sw);
     DfbCall bc = items ? *c.batch : DfbCall{};                     // the batch with its staging cells in place
     bc.nbmax = nbmax; bc.nsets = (uint32_t)nsets;
     for (int k = 0; k < MI_SETS; ++k) bc.stage[k] = t.stage[k];
@@ -703,9 +685,9 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         uint32_t *trec = t.trec ? t.trec + (size_t)k * nbmax * LZ_MAX_BLOCK : nullptr;
         {
             mi_prof_scope pr(ctx, "k_lz_parse_emit", sp, pbytes);
-            if (dict) hipLaunchKernelGGL((k_lz_parse_emit<true, true>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
-            else if (items) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
-            else hipLaunchKernelGGL(k_lz_parse_emit<false>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], lz_use_v2() ? 1 : 0, b0, trec);
+            if (dict) hipLaunchKernelGGL((k_lz_parse_emit<true, true>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
+            else if (items) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
+            else hipLaunchKernelGGL(k_lz_parse_emit<false>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
         }
         auto defh = [&] { mi_prof_scope ph(ctx, "k_defh_encode", sp, pbytes);     // mode H's entropy stage, the scan inside it: straight into the stream
                           defh_launch_encode(trec, sc[k].slot, sc[k].block_bits, nb, t.base_bits, d_block_bits + b0, d_out, cap_bytes, sp); };
@@ -733,15 +715,7 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         case LZ_BATCH:  defz(); place(); break;
         }
     };
-#ifdef MI_MEASURE
-    // measurement builds only (make EXTRA=-DMI_MEASURE): what would the step cost if a stage were free?  The stream is WRONG.
-    const int skip = getenv("MI_LZ_SKIP") ? atoi(getenv("MI_LZ_SKIP")) : 0;       // 1: no stage B, 2: no stage C, 3: neither
-#else
-    const int skip = 0;
-#endif
-    const hipStream_t sf_odd = lz_odd_fallback_stream(ctx, overlap, sb);
-    static const bool b_split = !(getenv("MI_LZ_B_SPLIT") && getenv("MI_LZ_B_SPLIT")[0] == '0');
-    const bool solo = !overlap && b_split && lz_use_v2() && !skip;
+    const hipStream_t sf_odd = lz_odd_fallback_stream(ctx, plan, sb);
     uint64_t batch = 0; uint32_t nb = 0;
     for (uint64_t b0 = 0; b0 < nblocks; b0 += nb, ++batch) {
         nb = (uint32_t)(nblocks - b0 < nbmax ? nblocks - b0 : nbmax);
@@ -752,21 +726,21 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         if (dict) { mi_prof_scope pr(ctx, "k_dfb_stage", s, (uint64_t)nb * P.block); dfb_launch_stage(bc, P.block, t.zws, b0, nb, s); }
         // stage A: partition + find on `s`, the fallback chain and the wide finder beside them
         const hipStream_t sf = !overlap ? (solo ? ctx->fb : s) : (batch & 1u) ? sf_odd : ctx->fb;
-        st = lz_find_stage_a(ctx, P, d_in, n, b0, nb, sc[k], sc2[k], s, sf, ctx->ev_part[k], ctx->ev_fb[k], ctx->ev_wide[k]);
+        st = lz_find_stage_a(ctx, P, d_in, n, b0, nb, sc[k], sc2[k], s, sf, ctx->ev_part[k], ctx->ev_fb[k], ctx->ev_wide[k], plan);
         if (st) return st;
         // stage B: the replays, behind the find and the wide parts' exports (lz_find.hip)
         if (overlap) {
             MI_HIP(ctx, hipEventRecord(ctx->ev_find[k], s)); MI_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_find[k], 0));
-            if (lz_use_v2()) MI_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_wide[k], 0));
+            if (v2) MI_HIP(ctx, hipStreamWaitEvent(sb, ctx->ev_wide[k], 0));
         }
-        if (solo) st = lz_stage_b_solo(ctx, P, nb, sc2[k], s);
-        else if (!(skip & 1)) st = lz_find_stage_b(ctx, P, nb, sc2[k], sb, 7);
+        if (solo) st = lz_stage_b_solo(ctx, P, nb, sc2[k], s, plan);
+        else if (!(skip & 1)) st = lz_find_stage_b(ctx, P, nb, sc2[k], sb, 7, plan);
         if (st) return st;
         // join: stage C needs the replays' results and the fallback blocks' candidates
         if (overlap) {
             MI_HIP(ctx, hipEventRecord(ctx->ev_replay[k], sb));
             MI_HIP(ctx, hipStreamWaitEvent(sp, ctx->ev_replay[k], 0));
-            if (lz_use_v2()) MI_HIP(ctx, hipStreamWaitEvent(sp, ctx->ev_fb[k], 0));
+            if (v2) MI_HIP(ctx, hipStreamWaitEvent(sp, ctx->ev_fb[k], 0));
         }
         if (!(skip & 2)) stage_c(k, b0, nb, batch);
         if (overlap) MI_HIP(ctx, hipEventRecord(ctx->ev_done[k], sp));

@@ -31,8 +31,7 @@
 // As the fallback of the LDS-resident finder these kernels normally have nothing to do, but every workgroup of a launch
 // must still be given its 82..155 KiB of LDS before it can find that out, and it takes that LDS from k_lz2_find
 // (rocprofv3, round 1: 1024-workgroup empty launches spent 4.8 ms each queueing).  So the bodies loop over the listed
-// blocks and the fallback launches use a small grid (LZ_FB_GRID workgroups).
-#define LZ_FB_GRID 128u
+// blocks and the fallback launches use a small grid (LZ_FB_GRID workgroups, lz_plan.h).
 #define DOM_DONE 0x80000000u                          // giant_list entry handled by k_lz_emulate_dom: k_lz_emulate_giant skips it
 template <bool DESC>
 __device__ __forceinline__ void lz_sort_home_block(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, LzScratch sc, uint64_t block0,
@@ -768,14 +767,17 @@ void k_lz_emulate_dom(LzP P, LzScratch sc, uint64_t *dbg)
 // =============================================================================================
 // host side of the match finder
 // =============================================================================================
-bool lz_use_v2()
+// The hint k_lz_sort_home leaves in pinned memory, read ONCE per call, at the entry point: two adjacent relaxed loads.  A kernel of
+// an earlier call may write the pair between them, so `fb` and `of` can come from two different batches; what follows from them is
+// a choice of streams and grid sizes, never a byte of output.
+LzHint lz_hint_read(const mi_ctx *ctx)
 {
-    const char *e = getenv("MI_LZ_V2");
-    return !(e && e[0] == '0');
+    if (!ctx->h_order) return LzHint{0u, 0u};
+    return LzHint{__atomic_load_n(ctx->h_order + 1, __ATOMIC_RELAXED), __atomic_load_n(ctx->h_order + 2, __ATOMIC_RELAXED)};
 }
 
 // one scratch set of nb blocks, both finders' arrays; sets start and end on multiples of 4096, so a call's sets are one stride apart
-void lz_carve(mi_carver &cv, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2)
+void lz_carve(mi_carver &cv, uint32_t nb, bool debug, LzScratch *sc, Lz2Scratch *sc2)
 {
     cv.off = mi_align_up(cv.off, 4096);
     sc->posA = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
@@ -789,25 +791,20 @@ void lz_carve(mi_carver &cv, uint32_t nb, LzScratch *sc, Lz2Scratch *sc2)
     sc->giant_cap = nb * LZ_MAX_GIANTS_PER_BLOCK;
     sc->slot = cv.take<uint32_t>((size_t)nb * LZ_SLOT_WORDS);
     sc->block_bits = cv.take<uint64_t>(nb + 1);
-    lz2_carve(cv, nb, sc2);
+    lz2_carve(cv, nb, debug, sc2);
     cv.off = mi_align_up(cv.off, 4096);
 }
 
 mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                        const LzScratch &sc, hipStream_t s, const uint32_t *blist, const uint32_t *bcount)
+                        const LzScratch &sc, hipStream_t s, const uint32_t *blist, const uint32_t *bcount, const LzPlan &plan)
 {
     // as the fallback of the LDS-resident finder these launches are normally empty and merely wait for LDS behind
     // k_lz2_find: timing them would report that wait as kernel time
     const int saved_prof = ctx->profiling;
-    static const bool prof_fb = getenv("MI_LZ_PROF_FALLBACK") != nullptr;      // inputs that live in the fallback (scripts/adv_profile.py)
-    if (blist && !prof_fb) ctx->profiling = 0;
+    if (blist && !plan.sw.prof_fallback) ctx->profiling = 0;                   // MI_LZ_PROF_FALLBACK: inputs that live in the fallback (scripts/adv_profile.py)
     MI_HIP(ctx, hipMemsetAsync(sc.giant_count, 0, 32, s));       // [0] / [2] clusters listed from the front / the end, [1] / [3] / [4] cursors (lz_common.h)
-    // fallback: few looping workgroups (see LZ_FB_GRID) — unless the last finished batch (in practice: of an earlier call) had
-    // many blocks here (non-text input): the count k_lz_sort_home left in pinned memory sizes the grids (pages family: half the
-    // chip sat idle behind 128 workgroups)
-    const uint32_t hint = (blist && ctx->h_order) ? __atomic_load_n(ctx->h_order + 1, __ATOMIC_RELAXED) : 0u;
-    const uint32_t fb_want = hint > LZ_FB_GRID ? hint : LZ_FB_GRID;
-    const uint32_t fgrid = (blist && nb > fb_want) ? fb_want : nb;
+    const LzFbGrids g = lz_plan_fallback_grids(plan, nb);       // sized by the call's hint (lz_plan.h)
+    const uint32_t fgrid = g.fgrid;
     {
         mi_prof_scope p(ctx, "k_lz_sort_home", s, (uint64_t)nb * P.block);
         if (P.flags & LZP_DESC) hipLaunchKernelGGL(k_lz_sort_home<true>, dim3(fgrid), dim3(1024), 0, s, d_in, n, P, sc, block0, nb, blist, bcount);
@@ -830,13 +827,8 @@ mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t
     }
     {
         mi_prof_scope p(ctx, "k_lz_emulate_giant", s, (uint64_t)nb * P.block);
-        const uint32_t cap = blist ? (hint > LZ_FB_GRID ? 512u : LZ_FB_GRID) : 1024u;
-        const uint32_t grid = nb < cap ? nb : cap;
-        if (blist && hint > 8u) {                           // blocks do fall back (lz_emit.hip's fb_busy): the clusters of <= LZ_GIANT_SMALL entries six workgroups per CU
-            const uint32_t gs = nb * 2u < (uint32_t)ctx->num_cu * 6u ? nb * 2u : (uint32_t)ctx->num_cu * 6u;
-            hipLaunchKernelGGL(k_lz_emulate_giant<LZ_GIANT_SMALL>, dim3(gs), dim3(256), 0, s, P, sc);
-        }
-        hipLaunchKernelGGL(k_lz_emulate_giant<LZ_GIANT_CAP>, dim3(grid), dim3(256), 0, s, P, sc);
+        if (g.small_grid) hipLaunchKernelGGL(k_lz_emulate_giant<LZ_GIANT_SMALL>, dim3(g.small_grid), dim3(256), 0, s, P, sc);
+        hipLaunchKernelGGL(k_lz_emulate_giant<LZ_GIANT_CAP>, dim3(g.giant_grid), dim3(256), 0, s, P, sc);
     }
     ctx->profiling = saved_prof;
     MI_HIP(ctx, hipGetLastError());
@@ -851,44 +843,37 @@ mi_status lz_find_batch(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t
 // sit in front of the real work waiting for that LDS.
 mi_status lz_find_stage_a(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                           const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s, hipStream_t sf, hipEvent_t ev_part, hipEvent_t ev_fb,
-                          hipEvent_t ev_wide)
+                          hipEvent_t ev_wide, const LzPlan &plan)
 {
-    if (!lz_use_v2()) return lz_find_batch(ctx, P, d_in, n, block0, nb, sc, s, nullptr, nullptr);
+    if (!plan.sw.v2) return lz_find_batch(ctx, P, d_in, n, block0, nb, sc, s, nullptr, nullptr, plan);
     mi_status st = lz2_stage_partition(ctx, P, d_in, n, block0, nb, sc2, s);
     if (st) return st;
-#ifdef MI_MEASURE
-    // measurement builds only (make EXTRA=-DMI_MEASURE): MI_LZ_UNSAFE_NO_FALLBACK=1 leaves the fallback chain out, to price its
-    // normally empty launches.  The output is WRONG for any block the partition hands back.
-    static const bool no_fb = getenv("MI_LZ_UNSAFE_NO_FALLBACK") != nullptr;
-#else
-    const bool no_fb = false;
-#endif
     if (sf != s) { MI_HIP(ctx, hipEventRecord(ev_part, s)); MI_HIP(ctx, hipStreamWaitEvent(sf, ev_part, 0)); }
     const bool wide_aside = sf != s && ev_wide;
     if (wide_aside) {
         // first thing on the side chain: stage B waits for it (exported clusters of wide parts), the fallback chain behind it does not matter
-        st = lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, sf, true);
+        st = lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, sf, true, plan);
         if (st) return st;
         MI_HIP(ctx, hipEventRecord(ev_wide, sf));
     }
-    if (!no_fb) {
-        st = lz_find_batch(ctx, P, d_in, n, block0, nb, sc, sf, sc2.fallback_list, sc2.fallback_count);
+    if (!plan.no_fallback) {
+        st = lz_find_batch(ctx, P, d_in, n, block0, nb, sc, sf, sc2.fallback_list, sc2.fallback_count, plan);
         if (st) return st;
     }
     if (sf != s) MI_HIP(ctx, hipEventRecord(ev_fb, sf));
     st = lz2_stage_find(ctx, P, d_in, n, block0, nb, sc2, s);
     if (st || wide_aside) return st;
-    return lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, s, false);
+    return lz2_stage_find_wide(ctx, P, d_in, n, block0, nb, sc2, s, false, plan);
 }
-mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which)
+mi_status lz_find_stage_b(mi_ctx *ctx, const LzP &P, uint32_t nb, const Lz2Scratch &sc2, hipStream_t s, int which, const LzPlan &plan)
 {
-    return lz_use_v2() ? lz2_stage_b(ctx, P, nb, sc2, s, which) : MI_OK;
+    return plan.sw.v2 ? lz2_stage_b(ctx, P, nb, sc2, s, which, plan) : MI_OK;
 }
 mi_status lz_run_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                      const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s)
+                      const LzScratch &sc, const Lz2Scratch &sc2, hipStream_t s, const LzPlan &plan)
 {
-    mi_status st = lz_find_stage_a(ctx, P, d_in, n, block0, nb, sc, sc2, s, s, nullptr, nullptr, nullptr);
-    return st ? st : lz_find_stage_b(ctx, P, nb, sc2, s, 7);
+    mi_status st = lz_find_stage_a(ctx, P, d_in, n, block0, nb, sc, sc2, s, s, nullptr, nullptr, nullptr, plan);
+    return st ? st : lz_find_stage_b(ctx, P, nb, sc2, s, 7, plan);
 }
 mi_status lz_check_params(const mi_lz_params *p)
 {
@@ -903,27 +888,6 @@ mi_status lz_check_params(const mi_lz_params *p)
     return MI_OK;
 }
 
-uint32_t lz_batch_blocks(mi_ctx *ctx, uint64_t nblocks)
-{
-    // As few, as large and as EQUAL batches as fit 3840 blocks (round 4).  The three-stream overlap buys 8 % over running every kernel
-    // alone, while every batch pays every kernel's tail: 10^8 B (1 526 blocks) in one batch 17.9 GB/s against 16.5 in two (1 024 + 502),
-    // 125 MB 18.4 / 17.6, 2 x 10^8 B 19.9 / 18.6, 3 x 10^8 B 20.5 (2 x 2 289) / 18.8 (1 024 x 4 + 482), 5 x 10^8 B 21.5 (2 x 3 815) / 20.8
-    // (2 048 x 3 + 1 486), 10^9 B 21.8-21.9 (4 x 3 815) / 21.7 (3 072 x 4 + 2 971) — same box, mode H.  (Until then: 1 024 below 6 144
-    // blocks, 2 048 below 9 216, else 3 072 — "as long as three stages have three batches to overlap".)  ~1.6 GB of workspace per 1 024
-    // blocks and set, three sets: 288 GB of HBM make that free; k_lz_scan_blocks holds a batch to 4 096 blocks.
-    const uint64_t nbat = (nblocks + 3839u) / 3840u;
-    uint64_t cap = nbat ? (nblocks + nbat - 1u) / nbat : 1u;
-    // ... unless the input lives in the fallback pipeline (the hint an earlier call left, lz_emit.hip: at least a sixteenth of a batch's
-    // blocks): its chains are long serial kernels on few workgroups, and what helps THEM is two batches' chains side by side on two
-    // streams — "runs" 4.7 GB/s in two batches against 3.8 in one, "pages" 3.5 / 3.4 (10^8 B): the old rule stays for such input
-    if (ctx && ctx->h_order) {
-        const uint32_t fb = __atomic_load_n(ctx->h_order + 1, __ATOMIC_RELAXED), of = __atomic_load_n(ctx->h_order + 2, __ATOMIC_RELAXED);
-        if (fb > 8u && (uint64_t)fb * 16u >= of) cap = nblocks >= 3u * 3072u ? 3072u : nblocks >= 3u * 2048u ? 2048u : 1024u;
-    }
-    if (const char *e = getenv("MI_LZ_BATCH")) { long v = atol(e); if (v >= 1 && v <= 4096) cap = (uint64_t)v; }
-    return (uint32_t)(nblocks < cap ? (nblocks ? nblocks : 1) : cap);
-}
-
 extern "C" mi_status mi_lz_find_all_dev(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
                                         uint16_t *d_cand, void *stream)
 {
@@ -934,15 +898,17 @@ extern "C" mi_status mi_lz_find_all_dev(mi_ctx *ctx, const mi_lz_params *p, cons
     hipStream_t s = (hipStream_t)stream;
     const LzP P = lz_params_of(ctx, p);
     const uint64_t nblocks = (n + P.block - 1) / P.block;
-    const uint32_t nbmax = lz_batch_blocks(ctx, nblocks);
+    const LzPlan plan = lz_plan(nblocks, (uint32_t)ctx->num_cu, lz_hint_read(ctx), lz_switches_read());
+    const uint32_t nbmax = plan.nbmax;
     LzScratch sc; Lz2Scratch sc2;
-    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve(cv, nbmax, &sc, &sc2); });
+    st = mi_ws_carve(ctx, [&](mi_carver &cv) { lz_carve(cv, nbmax, plan.sw.debug, &sc, &sc2); });
     if (st) return st;
+    lz2_set_switches(&sc2, plan.sw);
     for (uint64_t b0 = 0; b0 < nblocks; b0 += nbmax) {
         const uint32_t nb = (uint32_t)((nblocks - b0) < nbmax ? (nblocks - b0) : nbmax);
-        st = lz_run_find(ctx, P, d_in, n, b0, nb, sc, sc2, s);
+        st = lz_run_find(ctx, P, d_in, n, b0, nb, sc, sc2, s, plan);
         if (st) return st;
-        if (lz_use_v2()) lz2_launch_scatter(sc2, sc.cand, nb, s);
+        if (plan.sw.v2) lz2_launch_scatter(sc2, sc.cand, nb, s);
         // cand rows are LZ_MAX_BLOCK apart in scratch; the caller's array is block-size apart
         for (uint32_t i = 0; i < nb; ++i) {
             const uint64_t off = (b0 + i) * (uint64_t)P.block;
@@ -965,13 +931,14 @@ extern "C" mi_status mi_lz_find_all32_dev(mi_ctx *ctx, const mi_lz_params *p, co
     hipStream_t s = (hipStream_t)stream;
     const LzP P = lz_params_of(ctx, p);
     const uint64_t nblocks = (n + P.block - 1) / P.block;
+    const LzSwitches sw = lz_switches_read();
     uint32_t nbw = lzw_batch_blocks(ctx, nblocks, P.block);
     LzwScratch ws;
     st = lzw_reserve(ctx, &nbw, P.block, &ws, nullptr);
     if (st) return st;
     for (uint64_t b0 = 0; b0 < nblocks; b0 += nbw) {
         const uint32_t nb = (uint32_t)((nblocks - b0) < nbw ? (nblocks - b0) : nbw);
-        st = lzw_or_lzs_find(ctx, P, d_in, n, b0, nb, ws, s);
+        st = lzw_or_lzs_find(ctx, P, d_in, n, b0, nb, ws, s, sw);
         if (st) return st;
         for (uint32_t i = 0; i < nb; ++i) {
             const uint64_t off = (b0 + i) * (uint64_t)P.block;

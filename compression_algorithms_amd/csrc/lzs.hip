@@ -1044,7 +1044,7 @@ void k_lzs_big(LzP P, LzsScratch sc, uint32_t step, uint32_t cls)
 // The sliced finder lives in the arrays of lzw.hip's workspace (which it never uses at the same time): most as they are, its own
 // records carved inside eA and eB (nb x S x 8 bytes each).  *zero_bytes: what a batch zeroes from `counters` on — the counters
 // and the debug counters, not the flag list behind them.  false: a region is too small for what is carved in it.
-static bool lzs_view(const LzwScratch &ws, const LzP &P, uint32_t nb, LzsScratch *sc, size_t *zero_bytes)
+static bool lzs_view(const LzwScratch &ws, const LzP &P, uint32_t nb, bool debug, LzsScratch *sc, size_t *zero_bytes)
 {
     sc->key = ws.gid; sc->slot = ws.rd; sc->cand = ws.cand; sc->plist = ws.t_pos; sc->S = ws.S;
     const size_t region = (size_t)nb * ws.S * 8;
@@ -1059,17 +1059,16 @@ static bool lzs_view(const LzwScratch &ws, const LzP &P, uint32_t nb, LzsScratch
     sc->flag_list = b.take<uint32_t>(nb);                                // one word per block
     sc->flag_count = mi_carver::at(sc->counters, 64);
     sc->lb0 = 0;
-    sc->dbg = getenv("MI_LZ_DEBUG") ? dbg : nullptr;
+    sc->dbg = debug ? dbg : nullptr;                                     // (MI_LZ_DEBUG)
     sc->big_key = ws.t_mix; sc->big_info = ws.slot_of;                   // nb x S words each: a step has at most nb x S events
     for (uint32_t q = 0; q < LZS_NCLS; ++q) sc->big_desc[q] = ws.clist[q];  // nb x S / 2 + 64 each (a cluster has >= 17 events)
     return !a.overflow && !b.overflow;
 }
 
 // at most 64 steps per block (their work counters), event ids below 2^17; MI_LZW_SLICED=0 keeps lzw.hip's whole-block path (A/B, tests)
-bool lzs_applicable(const LzP &P)
+bool lzs_applicable(const LzP &P, bool sliced)
 {
-    const char *e = getenv("MI_LZW_SLICED");
-    if (e && e[0] == '0') return false;
+    if (!sliced) return false;
     const uint32_t W = 1u << P.wbits;
     // (coordinates relative to a part are sorted as 24-bit keys: a 2^24-bucket table plus the slots past its end would not fit)
     return !P.deflate && P.tbits <= 23u && (P.block + W - 1u) / W <= 64u;
@@ -1080,17 +1079,17 @@ bool lzs_applicable(const LzP &P)
 // their steps independently on the context's streams — one group's serial chains run beside another's sorts.
 // *flagged = blocks the sliced finder could not do (read back: one stream synchronisation per batch).
 mi_status lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
-                   const LzwScratch &ws, hipStream_t s, uint32_t *flagged, const uint32_t **flag_list)
+                   const LzwScratch &ws, hipStream_t s, uint32_t *flagged, const uint32_t **flag_list, const LzSwitches &sw)
 {
-    if (!lzs_applicable(P)) return MI_ERR_ARG;
+    if (!lzs_applicable(P, sw.lzw_sliced)) return MI_ERR_ARG;
     LzsScratch all; size_t zero_bytes;
-    if (!lzs_view(ws, P, nb, &all, &zero_bytes)) return MI_ERR_ARG;
+    if (!lzs_view(ws, P, nb, sw.debug, &all, &zero_bytes)) return MI_ERR_ARG;
     const uint32_t W = 1u << P.wbits;
     const uint32_t nsteps = (P.block + W - 1u) / W;
     const uint32_t chunks = (P.block + 256u * 16u - 1u) / (256u * 16u);
     // group g walks its steps on st[g]; the few long chains of a step (clusters above 512 events) run beside the many short
     // ones on the group's second stream ax[g] (a launch lasts as long as its longest chain)
-    const bool multi = ctx->side && ctx->parse && ctx->fb && !getenv("MI_LZS_SERIAL");       // MI_LZS_SERIAL=1: one stream (per-kernel times)
+    const bool multi = ctx->side && ctx->parse && ctx->fb && !sw.lzs_serial;                 // MI_LZS_SERIAL=1: one stream (per-kernel times)
     hipStream_t st[2] = {s, multi ? ctx->side : s}, ax[2] = {multi ? ctx->parse : s, multi ? ctx->fb : s};
     const uint32_t G = (nb < 2u || !multi) ? 1u : 2u;
     MI_HIP(ctx, hipMemsetAsync(all.counters, 0, zero_bytes, s));

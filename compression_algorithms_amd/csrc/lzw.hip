@@ -792,12 +792,13 @@ static LzwScratch lzw_view_at(const LzwScratch &ws, uint32_t lb)
 
 // The time-sliced LDS-resident finder (lzs.hip) first; a batch with a block it had to flag (a cluster above its capacity: long
 // runs of one byte value) is redone here, whole-block clusters of any size.
-mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s)
+mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb, const LzwScratch &sc, hipStream_t s,
+                          const LzSwitches &sw)
 {
-    if (lzs_applicable(P)) {
+    if (lzs_applicable(P, sw.lzw_sliced)) {
         uint32_t flagged = 0;
         const uint32_t *list = nullptr;
-        const mi_status st = lzs_find(ctx, P, d_in, n, block0, nb, sc, s, &flagged, &list);
+        const mi_status st = lzs_find(ctx, P, d_in, n, block0, nb, sc, s, &flagged, &list, sw);
         if (st) return st;
         if (!flagged) return MI_OK;
         if (list && flagged <= nb / 4u + 1u) {           // a few blocks with a giant cluster: only they are redone
@@ -805,7 +806,7 @@ mi_status lzw_or_lzs_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64
             const uint32_t k = flagged < 64u ? flagged : 64u;
             if (flagged <= 64u) {
                 for (uint32_t i = 0; i < k; ++i) todo[i] = list[i];          // (the pinned list is reused by later calls)
-                if (getenv("MI_LZ_DEBUG")) fprintf(stderr, "lzs: %u of %u blocks flagged, redone alone by the whole-block finder (first: %u)\n", flagged, nb, todo[0]);
+                if (sw.debug) fprintf(stderr, "lzs: %u of %u blocks flagged, redone alone by the whole-block finder (first: %u)\n", flagged, nb, todo[0]);
                 for (uint32_t i = 0; i < k; ++i) {
                     if (todo[i] >= nb) return MI_ERR_HIP;
                     const mi_status s2 = lzw_find(ctx, P, d_in, n, block0 + todo[i], 1u, lzw_view_at(sc, todo[i]), s);

@@ -471,8 +471,9 @@ def fallback_sequence():
     first call creates and the second finds in place), and the three streams are compared with the oracle's.  What this does
     NOT exercise: the release of that stream (hipStreamQuery in lz_emit.hip) — a call decides on it only once the hint is
     low again, which needs the text batches to have FINISHED, and then the input would no longer be late; it runs only in the
-    unchecked warm-up calls, on an idle stream.  MI_LZ_FB2_SIDE is read once per process, so the variants with it set run
-    this in a child process (python -c ... fallback_sequence())."""
+    unchecked warm-up calls, on an idle stream.  The encoder reads MI_LZ_FB2_SIDE with every call (csrc/lz_plan.h); the variants
+    with it set run this in a child process (python -c ... fallback_sequence()) all the same: a fresh process has a fresh
+    context, stream pool and hint."""
     import torch
     from compression_algorithms_amd.context import Context
     ctx = Context(0)

@@ -138,3 +138,36 @@ def test_warm_calls_on_two_fallback_streams_equal_the_oracle(family):
         print("path", ps)
     """, MI_LZ_BATCH="64")
     assert "path" in out
+
+
+def test_prof_fallback_switch_is_read_by_every_call(monkeypatch):
+    """The encoder reads its switches once per CALL, at the entry point (csrc/lz_plan.h) — also those that used to be read once
+    per process.  One process, one context, kernel profiling on, three blocks and 17 bytes of text in mode T: the fallback
+    chain's (empty) launches are timed while MI_LZ_PROF_FALLBACK is set and only then, and the stream is the oracle's each time."""
+    import numpy as np
+    from compression_algorithms_amd import lz, synth
+    from compression_algorithms_amd.context import Context
+    from oracle import orc
+    monkeypatch.delenv("MI_LZ_PROF_FALLBACK", raising=False)
+    data = synth.enwik_like(3 * 65536 + 17, seed=79).numpy()
+    p = lz.params("deflate")
+    want = orc.deflate_stream(data, p.block, True)[0]
+    ctx = Context(0)
+    try:
+        ctx.set_profiling(True)
+
+        def encode():
+            st = lz.compress(data, p, ctx)
+            ctx.sync()
+            assert np.array_equal(st.data[: st.nbytes].cpu().numpy(), want)
+            return {k["name"] for k in ctx.kernel_times()}               # (reading the times resets them)
+
+        names = encode()
+        assert "k_lz2_find" in names and "k_lz_sort_home" not in names, names
+        monkeypatch.setenv("MI_LZ_PROF_FALLBACK", "1")
+        assert "k_lz_sort_home" in encode()
+        monkeypatch.delenv("MI_LZ_PROF_FALLBACK")
+        names = encode()
+        assert "k_lz2_find" in names and "k_lz_sort_home" not in names, names
+    finally:
+        ctx.close()

@@ -175,8 +175,8 @@ def test_fallback_hint_and_second_fallback_stream(fb2_side, monkeypatch, tmp_pat
     """stream_cases.fallback_sequence.  With the switch unset the library decides from the hint alone where the odd batches'
     fallback chains go (with batches of 16 always the side stream: a hint above 8 is more than half a batch);
     MI_LZ_FB2_SIDE=0 makes the hint create the second fallback stream, which both text encodes then carry chains on; =1
-    sends the chains to the side stream.  The release of that stream is not exercised (fallback_sequence says why).  The
-    switch is read once per process, so those two run in a child process."""
+    sends the chains to the side stream.  The release of that stream is not exercised (fallback_sequence says why).  Those
+    two run in a child process (the switch is read with every call: the child is for a fresh context and hint)."""
     monkeypatch.setenv("MI_LZ_BATCH", "16")
     if fb2_side is None:
         monkeypatch.delenv("MI_LZ_FB2_SIDE", raising=False)
