@@ -37,7 +37,7 @@ class HuffmanTree(C.Structure):
 
 class LzParams(C.Structure):
     _fields_ = [("wbits", C.c_uint32), ("lbits", C.c_uint32), ("tbits", C.c_uint32), ("deflate", C.c_uint32),
-                ("block", C.c_uint32)]
+                ("block", C.c_uint32), ("parse", C.c_uint32)]         # parse: MI_PARSE_REFERENCE 0 (default), MI_PARSE_LAZY 1
 
 
 class FseParams(C.Structure):

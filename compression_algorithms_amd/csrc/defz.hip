@@ -595,12 +595,14 @@ mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_
     return hipGetLastError() == hipSuccess ? MI_OK : MI_ERR_HIP;
 }
 
-// mode Z takes the deflate flavour with distances and lengths RFC 1951 can code: wbits <= 15, lbits <= 8, blocks <= 64 KiB
+// mode Z takes the deflate flavour with distances and lengths RFC 1951 can code: wbits <= 15, lbits <= 8, blocks <= 64 KiB; the
+// lazy parse (its lengths do not come from the length field) with the deflate defaults wbits 15, lbits 5
 mi_status defz_check(const mi_lz_params *p, uint32_t container)
 {
-    mi_status st = lz_check_params(p);
+    mi_status st = lz_check_fields(p);
     if (st) return st;
     if (!p->deflate || p->wbits > 15 || p->lbits > 8 || p->block > LZ_MAX_BLOCK || container > MI_CONTAINER_GZIP) return MI_ERR_ARG;
+    if (p->parse > MI_PARSE_LAZY || (p->parse == MI_PARSE_LAZY && (p->wbits != 15 || p->lbits != 5))) return MI_ERR_ARG;
     return MI_OK;
 }
 

@@ -392,7 +392,7 @@ static mi_status block_encode_once(mi_ctx *ctx, const uint8_t *h_in, uint64_t n,
 extern "C" mi_status mi_lz_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
                                   uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits)
 {
-    if (!ctx || !h_out || !h_block_bits || (n && !h_in) || !p) return MI_ERR_ARG;
+    if (!ctx || !h_out || !h_block_bits || (n && !h_in) || !p || p->parse) return MI_ERR_ARG;
     return host_encode_with_retry(ctx, [&]() -> mi_status {
         const uint64_t nblocks = p->block ? (n + p->block - 1) / p->block : 0;
         const uint64_t bound = mi_lz_bound_bytes(n, p);
@@ -411,7 +411,7 @@ extern "C" mi_status mi_lz_encode(mi_ctx *ctx, const mi_lz_params *p, const uint
 extern "C" mi_status mi_deflate_h_encode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *h_in, uint64_t n,
                                          uint8_t *h_out, uint64_t cap_bytes, uint64_t *h_block_bits)
 {
-    if (!ctx || !p || !h_out || !h_block_bits || (n && !h_in) || !p->block) return MI_ERR_ARG;
+    if (!ctx || !p || !h_out || !h_block_bits || (n && !h_in) || !p->block || p->parse) return MI_ERR_ARG;
     return host_encode_with_retry(ctx, [&]() -> mi_status {
         bool done = false;
         const mi_status ps = mi_encode_host_pipelined(ctx, p, 1, h_in, n, h_out, cap_bytes, h_block_bits, &done);

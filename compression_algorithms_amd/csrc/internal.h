@@ -11,7 +11,8 @@
 size_t    huff_ws_bytes(uint64_t n);
 
 // ---- lz_find.hip: parameters, workspace and the stages of the match finder
-mi_status lz_check_params(const mi_lz_params *p);
+mi_status lz_check_params(const mi_lz_params *p);                      // parse 0 only
+mi_status lz_check_fields(const mi_lz_params *p);                      // every field but `parse` (for defz_check, which takes parse 1 too)
 // (what a call decides before it queues anything — LzSwitches, LzHint, LzPlan — is lz_plan.h: read once per call at the entry point)
 void      lz_carve(mi_carver &cv, uint32_t nb, bool debug, LzScratch *sc, Lz2Scratch *sc2);   // one scratch set; sets are multiples of 4096
 LzHint    lz_hint_read(const mi_ctx *ctx);

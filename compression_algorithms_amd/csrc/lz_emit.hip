@@ -23,7 +23,10 @@
 
 // DICT (with DESC): the first `skip` bytes of the block (LzBlkDesc) are a preset dictionary's tail — there for the finder, whose
 // candidates may point into it, and no part of the item: the parse starts at `skip` and only the item's tokens are counted and emitted
-template <bool DESC, bool DICT = false>              // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
+// PARSE 1 (mode Z's lazy parse, include/mi_codec.h; token records only): a length is the common prefix up to min(255, n - p) — no
+// byte at or past n is compared — and a position whose successor has the longer match becomes a literal; the chain p -> next(p) is
+// still a function of the position alone, so the exit tables resolve it, with entry offsets up to 254 instead of 30
+template <bool DESC, bool DICT = false, int PARSE = 0>   // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
 __global__ __launch_bounds__(1024)
 void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, LzScratch sc, Lz2Scratch s2, int use_v2,
                      uint64_t block0, uint32_t *__restrict__ trec_all)
@@ -33,7 +36,7 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     __shared__ __attribute__((aligned(16))) uint8_t s_L[LZ_MAX_BLOCK];
     __shared__ uint64_t s_tok[1024], s_mat[1024];
     __shared__ uint8_t  s_entry[1024];
-    __shared__ uint8_t  s_sexit[32][32];
+    __shared__ uint8_t  s_sexit[32][PARSE ? 256 : 32];
     __shared__ uint8_t  s_sentry[32];
     __shared__ uint32_t s_scan[18];
 
@@ -47,9 +50,21 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     const uint32_t skip = lz_block_skip<DICT>(in, block0, lb);
     const uint16_t *cand = sc.cand + (size_t)lb * LZ_MAX_BLOCK;
     const uint32_t W = 1u << P.wbits, max_len = (1u << P.lbits) - 1u;
+    // a candidate at this distance is no match (deflate lz77.c:223 / lz77.c:290); PARSE 1 is the deflate flavour with wbits 15
+    // (defz_check), its rule a constant
+    auto too_far = [&](uint32_t dist) -> bool {
+        if constexpr (PARSE != 0) return dist >= 32767u;
+        else return P.deflate ? (dist >= W - 1u) : (dist == W);
+    };
 
     // ---- block -> LDS with the zero tail
     lz_block_to_lds_of<DESC>(s_r0, src, n, (uint32_t)tid);
+    if constexpr (PARSE != 0) {
+        // behind the block every length is 0 (phase A writes positions below n only): position n counts as "no match" for the
+        // lazy step, and neither that step nor the exit tables need a bound of their own
+        for (uint32_t p = n + (uint32_t)tid; p < ((n + 15u) & ~15u); p += 1024u) s_L[p] = 0;
+        for (uint32_t q = ((n + 15u) >> 4) + (uint32_t)tid; q < LZ_MAX_BLOCK / 16u; q += 1024u) reinterpret_cast<uint4 *>(s_L)[q] = make_uint4(0, 0, 0, 0);
+    }
     if (tid == 0) s_L[LZ_MAX_BLOCK - 1] = 0;     // position 0xFFFF: its "pending" marker equals "none" (lz2.h); none unless a list says otherwise
     __syncthreads();
 
@@ -57,20 +72,27 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     // ---- A: token length at every position, were a token to start there.  The LDS-resident finder hands
     //      over (position, candidate) LISTS (coalesced); the first pipeline an array indexed by position.
     const bool lists = use_v2 && !s2.meta[lb].fallback;
+    // the most a match at p may cover: the length field's, or (PARSE 1) what one byte holds and the block has left
+    auto cap_of = [&](uint32_t p) -> uint32_t {
+        if constexpr (PARSE != 0) { const uint32_t r = n - p; return r < 255u ? r : 255u; }
+        else return max_len;
+    };
     auto token_len = [&](uint32_t p, uint32_t c) -> uint32_t {
+        const uint32_t cap = cap_of(p);                                     // (PARSE 1: the last compared word ends at n + 2 at most)
         uint32_t len = 0;
         if (c != LZ_NONE16) {
             const uint32_t dist = p - c;
-            const bool literal = P.deflate ? (dist >= W - 1u) : (dist == W);      // deflate lz77.c:223 / lz77.c:290
+            const bool literal = too_far(dist);
             if (!literal) {
                 len = 4;                                                        // the words are equal
                 // extend 4 bytes at a time (no `p < size` bound: the zero tail is there); first differing byte by ctz
-                while (len < max_len) {
+                while (len < cap) {
                     const uint32_t x = lds_word(s_r0, c + len) ^ lds_word(s_r0, p + len);
                     if (x) { len += (uint32_t)__builtin_ctz(x) >> 3; break; }
                     len += 4;
                 }
-                if (len > max_len) len = max_len;
+                if (len > cap) len = cap;
+                if constexpr (PARSE != 0) { if (len < 3u) len = 0; }           // (the equal words reach into the zero tail: 1 or 2 real bytes)
             }
         }
         return len;
@@ -111,13 +133,14 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     auto extend = [&](uint32_t item, bool on) {
         if (on) {
             const uint32_t p = item & 0xFFFFu, c = item >> 16;
+            const uint32_t cap = cap_of(p);
             uint32_t len = 8;
-            while (len < max_len) {
+            while (len < cap) {
                 const uint32_t x = lds_word(s_r0, c + len) ^ lds_word(s_r0, p + len);
                 if (x) { len += (uint32_t)__builtin_ctz(x) >> 3; break; }
                 len += 4;
             }
-            s_L[p] = (uint8_t)(len > max_len ? max_len : len);
+            s_L[p] = (uint8_t)(len > cap ? cap : len);
         }
     };
     auto enqueue = [&](bool ext, uint32_t item) {
@@ -150,18 +173,22 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
                 for (int k = 0; k < 8; ++k) {
                     pp[k] = (wp[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu; cc[k] = (wc[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
                     const uint32_t dist = pp[k] - cc[k];
-                    // a candidate that the literal rule does not reject (deflate lz77.c:223 / lz77.c:290); c == p: pending or pad
-                    act[k] = full && cc[k] != LZ_NONE16 && cc[k] != pp[k] && !(P.deflate ? (dist >= W - 1u) : (dist == W));
+                    // a candidate that the literal rule does not reject; c == p: pending or pad
+                    act[k] = full && cc[k] != LZ_NONE16 && cc[k] != pp[k] && !too_far(dist);
                     xx[k] = 0;
                 }
 #pragma unroll
                 for (int k = 0; k < 8; ++k) if (act[k]) xx[k] = lds_word(s_r0, cc[k] + 4u) ^ lds_word(s_r0, pp[k] + 4u);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const bool ext = act[k] && xx[k] == 0u && max_len > 8u;
+                    const uint32_t cap = cap_of(pp[k]);
+                    const bool ext = act[k] && xx[k] == 0u && cap > 8u;
                     if (full && cc[k] != pp[k] && !ext) {              // (pending / pad: the other list, or nobody, writes it)
                         uint32_t len = 0;
-                        if (act[k]) { len = xx[k] ? 4u + ((uint32_t)__builtin_ctz(xx[k]) >> 3) : 8u; if (len > max_len) len = max_len; }
+                        if (act[k]) {
+                            len = xx[k] ? 4u + ((uint32_t)__builtin_ctz(xx[k]) >> 3) : 8u; if (len > cap) len = cap;
+                            if constexpr (PARSE != 0) { if (len < 3u) len = 0; }
+                        }
                         s_L[pp[k]] = (uint8_t)len;
                     }
                     enqueue(ext, pp[k] | (cc[k] << 16));
@@ -199,11 +226,32 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
 #pragma unroll
             for (int q = 0; q < 4; ++q) { const uint4 v = lp[q]; lw[4 * q] = v.x; lw[4 * q + 1] = v.y; lw[4 * q + 2] = v.z; lw[4 * q + 3] = v.w; }
         }
+        if constexpr (PARSE != 0) {
+            // the lazy step: a match gives way to a literal where the next position's match is longer.  Every thread has its 64
+            // lengths and the first of the next chunk in registers BEFORE anyone writes (in place, a neighbour would read a length
+            // already rewritten); position n and everything behind it are 0 (filled above), and there is no s_L[65536]
+            const uint32_t nx0 = c < 1023u ? (uint32_t)s_L[c * 64u + 64u] : 0u;
+            __syncthreads();
+            uint32_t ew[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) ew[q] = 0;
+#pragma unroll
+            for (int o = 0; o < 64; ++o) {
+                const uint32_t l = (lw[o >> 2] >> (8 * (o & 3))) & 0xFFu;
+                const uint32_t nl = o < 63 ? (lw[(o + 1) >> 2] >> (8 * ((o + 1) & 3))) & 0xFFu : nx0;
+                ew[o >> 2] |= (nl > l ? 0u : l) << (8 * (o & 3));
+            }
+            uint4 *wp = reinterpret_cast<uint4 *>(s_L + c * 64u);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { wp[q] = make_uint4(ew[4 * q], ew[4 * q + 1], ew[4 * q + 2], ew[4 * q + 3]); }
+#pragma unroll
+            for (int q = 0; q < 16; ++q) lw[q] = ew[q];
+        }
 #pragma unroll
         for (int o = 63; o >= 0; --o) {
             const uint32_t p = c * 64u + (uint32_t)o;
             uint32_t e = 0;
-            if (p < n) {
+            if (PARSE != 0 || p < n) {                              // (PARSE 1: the lengths behind the block are 0, their exits harmless)
                 const uint32_t l = (lw[o >> 2] >> (8 * (o & 3))) & 0xFFu;
                 const uint32_t nx = (uint32_t)o + (l ? l : 1u);
                 e = nx >= 64u ? nx - 64u : ex[nx * 1024u + c];
@@ -215,8 +263,32 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     PE_TICK(2);
     // compose over super-chunks of 32 chunks.  A chunk is entered at offset <= max_len - 1 <= 30 for the
     // reference's length fields (lbits 4 and 5); longer fields take the serial walk below.
-    const bool wide = max_len > 31u;
-    if (!wide) {
+    const bool wide = PARSE != 0 ? false : max_len > 31u;
+    if constexpr (PARSE != 0) {
+        // a chunk is entered at an offset up to 254, and an offset of 64 or more passes the whole chunk: 32 super-chunks x 256
+        // entry offsets, eight independent walks per thread (their LDS round trips overlap)
+        const uint32_t scn = tid >> 5, o = tid & 31u;
+        uint32_t x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = o + 32u * (uint32_t)j;
+        for (uint32_t c = scn * 32u; c < scn * 32u + 32u; ++c) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = x[j] >= 64u ? x[j] - 64u : ex[x[j] * 1024u + c];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s_sexit[scn][o + 32u * (uint32_t)j] = (uint8_t)x[j];
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t e = 0;
+            for (uint32_t s = 0; s < 32; ++s) { s_sentry[s] = (uint8_t)e; e = s_sexit[s][e]; }
+        }
+        __syncthreads();
+        if (tid < 32) {
+            uint32_t xx = s_sentry[tid];
+            for (uint32_t c = tid * 32u; c < tid * 32u + 32u; ++c) { s_entry[c] = (uint8_t)xx; xx = xx >= 64u ? xx - 64u : ex[xx * 1024u + c]; }
+        }
+        __syncthreads();
+    } else if (!wide) {
         const uint32_t scn = tid >> 5, o = tid & 31u;
         uint32_t x = o;
         for (uint32_t c = scn * 32u; c < scn * 32u + 32u; ++c) x = ex[x * 1024u + c];
@@ -298,7 +370,7 @@ void k_lz_parse_emit(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     const uint32_t LB = P.deflate ? 16u : 9u, MB = P.deflate ? 32u : (1u + P.wbits + P.lbits);
     uint32_t *slot = sc.slot + (size_t)lb * LZ_SLOT_WORDS;
     uint32_t carry = 0;
-    if (trec_all) {
+    if (PARSE != 0 || trec_all) {                                  // (PARSE 1 has no packed form)
         // mode H (defh.hip): no packed tokens; one 32-bit record per token, in token order, for the entropy stage:
         //   literal  byte                       match  1<<31 | length << 16 | distance
         // The 286-bin tally of the block (deflate/lz77.c:206,231,273; deflate/huffman.c:49-62) is taken here, where every
@@ -626,7 +698,8 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
 {
     const bool items = c.form == LZ_BATCH;                         // a batch of independent items brings its own buffers
     if (!ctx || (!items && (!d_out || !d_block_bits || (n && !d_in)))) return MI_ERR_ARG;
-    mi_status st = lz_check_params(p);
+    const bool zform = c.form == LZ_Z || c.form == LZ_BGZF || c.form == LZ_BATCH;      // mode Z's records: the forms that take parse 1
+    mi_status st = zform ? defz_check(p, c.container) : lz_check_params(p);
     if (st) return st;
     if (!items && ((uintptr_t)d_out & 3u) != 0) return MI_ERR_ARG;
     if (c.form == LZ_H && (!p->deflate || p->lbits > 5 || p->wbits > 16)) return MI_ERR_ARG;
@@ -685,7 +758,12 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         uint32_t *trec = t.trec ? t.trec + (size_t)k * nbmax * LZ_MAX_BLOCK : nullptr;
         {
             mi_prof_scope pr(ctx, "k_lz_parse_emit", sp, pbytes);
-            if (dict) hipLaunchKernelGGL((k_lz_parse_emit<true, true>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
+            if (P.flags & LZP_LAZY) {                                  // mode Z's parse 1 (forms with token records only: checked at the entry)
+                if (dict) hipLaunchKernelGGL((k_lz_parse_emit<true, true, 1>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
+                else if (items) hipLaunchKernelGGL((k_lz_parse_emit<true, false, 1>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
+                else hipLaunchKernelGGL((k_lz_parse_emit<false, false, 1>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
+            }
+            else if (dict) hipLaunchKernelGGL((k_lz_parse_emit<true, true>), dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
             else if (items) hipLaunchKernelGGL(k_lz_parse_emit<true>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
             else hipLaunchKernelGGL(k_lz_parse_emit<false>, dim3(nb), dim3(1024), 0, sp, d_in, n, P, sc[k], sc2[k], v2, b0, trec);
         }

@@ -878,6 +878,12 @@ mi_status lz_run_find(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n
 mi_status lz_check_params(const mi_lz_params *p)
 {
     if (!p) return MI_ERR_ARG;
+    if (p->parse != MI_PARSE_REFERENCE) return MI_ERR_ARG;         // another parse is mode Z's alone: defz_check lets it through
+    return lz_check_fields(p);
+}
+mi_status lz_check_fields(const mi_lz_params *p)
+{
+    if (!p) return MI_ERR_ARG;
     if (p->wbits < 8 || p->wbits > 16) return MI_ERR_ARG;
     if (p->lbits < 3 || p->lbits > 8) return MI_ERR_ARG;
     if (p->tbits < 17 || p->tbits > 24) return MI_ERR_ARG;

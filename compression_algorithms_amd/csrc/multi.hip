@@ -303,7 +303,7 @@ static void *multi_worker(void *arg)
 static mi_status multi_encode(mi_multi *m, const mi_lz_params *p, int mode_h, const uint8_t *const *d_in, const uint8_t *h_in, uint64_t n,
                               uint8_t *d_out0, uint64_t cap_bytes, uint64_t *d_block_bits0)
 {
-    if (!m || !p || !d_out0 || !d_block_bits0 || (n && !d_in && !h_in) || !p->block) return MI_ERR_ARG;
+    if (!m || !p || !d_out0 || !d_block_bits0 || (n && !d_in && !h_in) || !p->block || p->parse) return MI_ERR_ARG;
     // (blocks above 64 KiB — the lz77 flavour's sliced finder — synchronise their stream once per batch: harmless here, every device
     //  has its own host thread)
     if (((uintptr_t)d_out0 & 3u) != 0) return MI_ERR_ARG;

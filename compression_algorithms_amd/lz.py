@@ -15,12 +15,14 @@ from . import _lib
 from .context import as_device_bytes, default_context
 
 
-def params(flavour="deflate", wbits=None, block=65536):
+def params(flavour="deflate", wbits=None, block=65536, parse=0):
+    """parse: 0 the reference's greedy parse; 1 the lazy parse with matches up to 255 bytes, for the standard-DEFLATE writers
+    only (compress_z, compress_bgzf, deflate_batch and their host forms; include/mi_codec.h, mode Z)"""
     if flavour == "deflate":
-        return _lib.LzParams(15, 5, 20, 1, block)
+        return _lib.LzParams(15, 5, 20, 1, block, parse)
     if flavour == "lz77":
         wb = 14 if wbits is None else wbits
-        return _lib.LzParams(wb, 4, wb + 6, 0, block)
+        return _lib.LzParams(wb, 4, wb + 6, 0, block, parse)
     raise ValueError(flavour)
 
 

@@ -180,10 +180,17 @@ typedef struct {
     uint32_t deflate;     /* 1: deflate rules (insert probe wraps, literal iff p-m >= W-1, byte tokens) */
     uint32_t block;       /* block size in bytes: 1..65536; lz77 flavour also 65792..1048576 in steps of 256 —
                            * the HBM-resident finder of lzw.hip, where a 64 KiB window really slides (exact, slower) */
+    uint32_t parse;       /* MI_PARSE_REFERENCE (0, what every initialiser below leaves): the reference's greedy parse.
+                           * MI_PARSE_LAZY (1): mode Z's lazy parse with matches up to 255 bytes — the standard-DEFLATE
+                           * writers only (mode Z, BGZF, the batched deflate); MI_ERR_ARG everywhere else */
 } mi_lz_params;
+#define MI_PARSE_REFERENCE 0
+#define MI_PARSE_LAZY      1
 
-static inline mi_lz_params mi_lz_params_deflate(void) { mi_lz_params p = {15, 5, 20, 1, 65536}; return p; }
-static inline mi_lz_params mi_lz_params_lz77(uint32_t wbits) { mi_lz_params p = {wbits, 4, wbits + 6, 0, 65536}; return p; }
+static inline mi_lz_params mi_lz_params_deflate(void) { mi_lz_params p = {15, 5, 20, 1, 65536, MI_PARSE_REFERENCE}; return p; }
+static inline mi_lz_params mi_lz_params_lz77(uint32_t wbits) { mi_lz_params p = {wbits, 4, wbits + 6, 0, 65536, MI_PARSE_REFERENCE}; return p; }
+/* the deflate flavour with the parse chosen: mi_lz_params_deflate_parse(MI_PARSE_LAZY) for mode Z, BGZF and the batched deflate */
+static inline mi_lz_params mi_lz_params_deflate_parse(uint32_t parse) { mi_lz_params p = {15, 5, 20, 1, 65536, parse}; return p; }
 
 static inline uint64_t mi_lz_num_blocks(uint64_t n, const mi_lz_params *p) { return (n + p->block - 1) / p->block; }
 /* bound on the concatenated stream, in bytes.  Per block: every byte a literal (2 bytes / 9 bits), except that the
@@ -309,6 +316,17 @@ mi_status mi_deflate_h_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t 
  * min(rest, 6) while rest >= 3; whatever is left of a run is written as plain lengths.  The stream
  * ends with 03 00 (a final fixed block with only end-of-block); for n = 0 the raw stream is just
  * 03 00.  oracle/orc_defz.c restates all of this on the CPU; the encoder gives its bytes.
+ * Parse 1 (p->parse == MI_PARSE_LAZY; wbits 15, lbits 5): other tokens, everything behind them as above.  Per block of n
+ * bytes, skip = the bytes of a preset dictionary's tail in front of an item's first block (else 0), cand[p] the finder's
+ * answer at p as for parse 0:
+ *   len0(p) = 0 if there is no candidate or p - cand[p] >= 32767 (the literal rule, unchanged); else the length l of the
+ *             common prefix of in[cand[p]..] and in[p..], at most min(255, n - p) — no byte at or past n is compared, no
+ *             match runs past the block, so nothing is ever clipped; 0 if l < 3.  len0(n) = 0.
+ *   eff(p)  = 0 if len0(p) == 0 or len0(p + 1) > len0(p) (a one-step lazy rule: the longer match one byte on wins),
+ *             else len0(p).
+ *   walk:     p = skip; while p < n: eff(p) ? match (eff(p), p - cand[p]), p += eff(p) : literal in[p], p += 1.
+ * The streams are standard DEFLATE as before and smaller (text about 2 %, zero pages and runs several times); they
+ * are no longer the reference's tokens.  The bounds do not change: stored is still the ceiling.
  * Containers: MI_CONTAINER_RAW the above; MI_CONTAINER_ZLIB 78 9C, the raw stream, Adler-32
  * big-endian; MI_CONTAINER_GZIP 1F 8B 08 00 00 00 00 00 00 FF (no flags, MTIME 0, OS 255: the
  * output is reproducible), the raw stream, CRC-32 little-endian, ISIZE = n mod 2^32 little-endian.
@@ -316,8 +334,8 @@ mi_status mi_deflate_h_decode(mi_ctx *ctx, const mi_lz_params *p, const uint8_t 
  * container header included, so entry 0 is 0, 16 or 80; all multiples of 8); entry nblocks is where
  * the final 03 00 starts.  Every record can be inflated on its own from there: restart points.
  * *d_out_bytes: the total length in bytes (on the device, like the table).
- * p: deflate flavour with wbits <= 15, lbits <= 8, block <= 65 536; anything else, or an unknown
- * container, is MI_ERR_ARG.  d_out 4-byte aligned; cap_bytes below mi_deflate_z_bound_bytes is
+ * p: deflate flavour with wbits <= 15, lbits <= 8, block <= 65 536, parse 0 or 1 (1: wbits 15 and
+ * lbits 5); anything else, or an unknown container, is MI_ERR_ARG.  d_out 4-byte aligned; cap_bytes below mi_deflate_z_bound_bytes is
  * MI_ERR_CAPACITY.
  * ------------------------------------------------------------------------------------ */
 #define MI_CONTAINER_RAW  0u

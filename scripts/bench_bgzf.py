@@ -3,7 +3,7 @@ process.  Encode: mi_bgzf_encode_dev (block 65 280) against mi_deflate_z_encode_
 mi_bgzf_index_dev and mi_bgzf_inflate_dev, timed separately, against mi_inflate_dev on the mode-Z gzip stream of the same
 input with its table.  One JSON line.
 
-    python scripts/bench_bgzf.py [--bytes 1000000000] [--repeats 5]
+    python scripts/bench_bgzf.py [--bytes 1000000000] [--repeats 5] [--parse {0,1}]
 """
 import argparse
 import ctypes as C
@@ -36,10 +36,11 @@ def main():
     ap.add_argument("--bytes", type=int, default=1_000_000_000)
     ap.add_argument("--seed", type=int, default=12345)            # bench.py's corpus
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--parse", type=int, choices=(0, 1), default=0)   # the parse of both encoders (include/mi_codec.h, mode Z)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     ctx = lz.default_context()
-    pz, pb = lz.params("deflate"), lz.params("deflate", block=lz.BGZF_BLOCK)
+    pz, pb = lz.params("deflate", parse=a.parse), lz.params("deflate", block=lz.BGZF_BLOCK, parse=a.parse)
     x = synth.enwik_like(a.bytes, seed=a.seed, device=dev)
     n = x.numel()
     nbz, nbb = (n + pz.block - 1) // pz.block, (n + pb.block - 1) // pb.block
@@ -119,6 +120,7 @@ def main():
     res["device"] = torch.cuda.get_device_name(0)
     res["bytes"] = n
     res["repeats"] = a.repeats
+    res["parse"] = a.parse
     print(json.dumps(res))
 
 

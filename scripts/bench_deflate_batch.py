@@ -136,7 +136,7 @@ def dict_child(a):
     """--dict in this process (under whatever MI_CODEC_LIB the parent set): prints its own JSON line"""
     import zlib
     ctx = lz.default_context()
-    p = lz.params("deflate")
+    p = lz.params("deflate", parse=a.parse)
     x = synth.enwik_like(a.bytes, seed=a.seed).numpy().tobytes()
     zd, body = x[:DICT_BYTES], x[DICT_BYTES:]
     offs = list(range(0, len(body) - a.dict_item + 1, a.dict_item))
@@ -174,7 +174,7 @@ def child(a):
     if a.child in ("dict", "dict-parent"):
         return dict_child(a)
     ctx = lz.default_context()
-    p = lz.params("deflate")
+    p = lz.params("deflate", parse=a.parse)
     if a.child == "skewed":
         x = synth.enwik_like(max(a.skew_small * 4096, a.skew_big << 20), seed=a.seed).numpy().tobytes()
         pieces = [x[i * 4096:(i + 1) * 4096] for i in range(a.skew_small)]
@@ -229,15 +229,16 @@ def main():
     ap.add_argument("--dict", action="store_true")
     ap.add_argument("--dict-item", type=int, default=700)
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--parse", type=int, choices=(0, 1), default=0)   # the parse of every encode (include/mi_codec.h, mode Z)
     a = ap.parse_args()
     if a.child:
         return child(a)
-    res = dict(device=torch.cuda.get_device_name(0), bytes=a.bytes, repeats=a.repeats)
+    res = dict(device=torch.cuda.get_device_name(0), bytes=a.bytes, repeats=a.repeats, parse=a.parse)
     if a.dict:
         for case in ("dict", "dict-parent") if a.parent_lib else ("dict",):
             env = dict(os.environ, MI_CODEC_LIB=os.path.abspath(a.parent_lib)) if case == "dict-parent" else dict(os.environ)
             c = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case, "--bytes", str(a.bytes), "--repeats", str(a.repeats),
-                                "--seed", str(a.seed), "--dict-item", str(a.dict_item)], capture_output=True, text=True, timeout=900, env=env)
+                                "--seed", str(a.seed), "--dict-item", str(a.dict_item), "--parse", str(a.parse)], capture_output=True, text=True, timeout=900, env=env)
             assert c.returncode == 0, c.stderr[-2000:]
             res[case.replace("-", "_")] = json.loads(c.stdout.strip().splitlines()[-1])
         res["dict_over_no_dict"] = round(res["dict"]["dict"]["ms_median"] / res["dict"]["no_dict"]["ms_median"], 4)
@@ -247,7 +248,7 @@ def main():
         return
     for case in ("uniform", "aligned", "skewed"):
         c = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case, "--bytes", str(a.bytes), "--repeats", str(a.repeats),
-                            "--seed", str(a.seed), "--skew-small", str(a.skew_small), "--skew-big", str(a.skew_big)],
+                            "--seed", str(a.seed), "--skew-small", str(a.skew_small), "--skew-big", str(a.skew_big), "--parse", str(a.parse)],
                            capture_output=True, text=True, timeout=900)
         assert c.returncode == 0, c.stderr[-2000:]
         res[case] = json.loads(c.stdout.strip().splitlines()[-1])

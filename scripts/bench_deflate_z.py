@@ -3,7 +3,9 @@ one process; zlib.compress levels 1 and 6 on one host core as the CPU baseline. 
 inflater (mi_inflate_dev) on the raw and gzip streams, with and without its checksum pass, against mode H's decoder, and
 zlib.decompress on one host core.
 
-    python scripts/bench_deflate_z.py [--bytes 1000000000] [--repeats 5] [--cpu-bytes 100000000]
+    python scripts/bench_deflate_z.py [--bytes 1000000000] [--repeats 5] [--cpu-bytes 100000000] [--parse {0,1}]
+
+--parse 1: mode Z with the lazy parse and matches up to 255 bytes (mode H keeps the reference's tokens).
 """
 import argparse
 import ctypes as C
@@ -25,17 +27,18 @@ def main():
     ap.add_argument("--seed", type=int, default=12345)            # bench.py's corpus
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--cpu-bytes", type=int, default=100_000_000)
+    ap.add_argument("--parse", type=int, choices=(0, 1), default=0)   # mode Z's parse (include/mi_codec.h)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     ctx = lz.default_context()
-    p = lz.params("deflate")
+    p, pz = lz.params("deflate"), lz.params("deflate", parse=a.parse)          # mode H, mode Z
     x = synth.enwik_like(a.bytes, seed=a.seed, device=dev)
     n = x.numel()
     nblocks = (n + p.block - 1) // p.block
     bits = torch.zeros(nblocks + 2, dtype=torch.int64, device=dev)
     s = ctx.stream_ptr()
     cap_h = int(ctx.L.mi_deflate_h_bound_bytes(n, C.byref(p))) + 64
-    cap_z = max(lz.bound_bytes_z(n, p, c) for c in (0, 2)) + 64
+    cap_z = max(lz.bound_bytes_z(n, pz, c) for c in (0, 2)) + 64
     out = torch.empty(max(cap_h, cap_z), dtype=torch.uint8, device=dev)
     xp, op, bp, ob = C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(bits.data_ptr()), C.c_void_p(bits[nblocks + 1:].data_ptr())
 
@@ -45,7 +48,7 @@ def main():
 
     def run_z(c):
         def f():
-            assert ctx.L.mi_deflate_z_encode_dev(ctx.h, C.byref(p), c, xp, n, op, cap_z, bp, ob, s) == 0
+            assert ctx.L.mi_deflate_z_encode_dev(ctx.h, C.byref(pz), c, xp, n, op, cap_z, bp, ob, s) == 0
             return lambda: int(bits[nblocks + 1].item())
         return f
 
@@ -111,7 +114,7 @@ def main():
         res[m] = dict(ms_median=round(med, 3), ms_min=round(t[0], 3), gbps=round(n / med / 1e6, 3))
     res["mode_z_decode_over_mode_h_decode"] = round(res["mode_z_decode_raw"]["gbps"] / res["mode_h_decode"]["gbps"], 3)
     cpu = x[: a.cpu_bytes].cpu().numpy().tobytes()
-    zc = streams["mode_z_gzip"][0].cpu().numpy().tobytes() if a.cpu_bytes >= n else lz.compress_z(x[: a.cpu_bytes], p, "gzip").tobytes()
+    zc = streams["mode_z_gzip"][0].cpu().numpy().tobytes() if a.cpu_bytes >= n else lz.compress_z(x[: a.cpu_bytes], pz, "gzip").tobytes()
     t0 = time.perf_counter()
     back = zlib.decompress(zc, 31)
     dt = time.perf_counter() - t0
@@ -125,6 +128,7 @@ def main():
     res["device"] = torch.cuda.get_device_name(0)
     res["bytes"] = n
     res["repeats"] = a.repeats
+    res["parse"] = a.parse
     print(json.dumps(res))
 
 
