@@ -40,6 +40,7 @@ struct mi_ctx {
     int         lds_rank_ok = 0;       // LDS returning atomics serve the lanes of one instruction in lane order (self-check at creation)
     int         test_break_rank = 0;   // MI_LZ_TEST_BREAK_RANK=1: the scatter mis-ranks on purpose (tests of the order check)
     int         test_force_fb = 0;     // MI_LZ_TEST_FORCE_FALLBACK=1 (lib_test only): every block goes to the fallback pipeline
+    int         test_small_parts = 0;  // MI_LZ_TEST_SMALL_PARTS=1 (lib_test only): parts of at most 640 entries (lz2_partition.hip)
     uint64_t   *d_stats = nullptr;     // device counters behind mi_lz_path_stats: [0] fallback blocks, [1] wide parts
     uint32_t   *h_order = nullptr;     // pinned, device-visible: set by a kernel that found a sort out of order (lz_common.h)
     uint32_t   *d_order = nullptr;     // the same word as the device addresses it
@@ -50,6 +51,8 @@ struct mi_ctx {
     size_t      ws_bytes = 0;
 #ifdef MI_TEST_HOOKS
     size_t      ws_asked = 0;          // lib_test only: the largest request since mi_test_ws_guard's reset (ctx.hip)
+    const void *test_partmap = nullptr, *test_partmap_meta = nullptr;   // lib_test only: what the last partition launch wrote, and its
+    uint32_t    test_partmap_nb = 0;                                    // blocks (mi_test_partmap, lz2_find.hip)
 #endif
     // small pinned host staging area for info structs
     void       *h_pinned = nullptr;

@@ -1,6 +1,7 @@
 // lz2.h — data structures of the LDS-resident match finder (lz2_partition.hip, lz2_find.hip).
 #pragma once
 #include "lz_common.h"
+#include "partmap_planes.h"
 
 #define LZ2_NG_BITS   14
 #define LZ2_NG        (1u << LZ2_NG_BITS)   // bucket groups per block for the overflow certificate
@@ -25,6 +26,9 @@
 #define LZ2_PARTBITS  7                     // parts per block <= 2^LZ2_PARTBITS (one radix digit of stage 1)
 #endif
 #define LZ2_MAXPARTS  (1u << LZ2_PARTBITS)
+// the part map (partmap_planes.h) keeps PMP_PLANES bits per position and the all-ones code for "no position": the partition's
+// guard `k + 2 > LZ2_MAXPARTS` lets a block have at most LZ2_MAXPARTS - 1 parts, numbered 0 .. LZ2_MAXPARTS - 2 — never that code
+static_assert(LZ2_MAXPARTS - 1u == PMP_NONE && (1u << PMP_PLANES) == LZ2_MAXPARTS, "part numbers must fit the planes and leave the code of no position free");
 static_assert(LZ2_CAP % LZ2_THREADS == 0 && LZ2_CAP_S % LZ2_THREADS == 0 && LZ2_CAP_S <= LZ2_CAP, "entries per thread must be whole");
 // The greedy cuts of k_lz2_partition can never run out of part numbers.  A part ends at the LAST certified group that keeps it
 // within LZ2_CAP_S entries and (2^20-bucket tables) within 2^16 homes; so for two consecutive parts either their entries
@@ -87,7 +91,8 @@ struct Lz2BigDesc {
 };
 
 struct Lz2Scratch {
-    uint8_t      *partmap;      // [nb][65536] part of every position (0xFF past the block's end): written by the partition, scanned by stage 2
+    uint32_t     *partmap;      // [nb][7 planes][2048] the part of every position as bit planes (partmap_planes.h; the code 127 past the block's
+                                // end): written by the partition, scanned by stage 2
     uint16_t     *plist;        // [nb][65536] positions, grouped by part, time order inside a part: written by stage 2 for the parse
     uint16_t     *cand;         // [nb][65536] find() result aligned with plist (own position = pending: see bigcand)
     Lz2BlockMeta *meta;         // [nb]

@@ -198,34 +198,35 @@ __device__ __forceinline__ void lz2_find_part(const uint8_t *__restrict__ in, ui
     static_assert(sizeof(s_cnt) <= sizeof(s_gr), "the second pass's radix counters must fit s_g | s_r");
     constexpr uint32_t RST = LZ2_NWAVES + 1;                                        // counter stride of radix_pass
     const uint32_t seg = radix_seg<LZ2_NWAVES>(m), seg_inv = (uint32_t)((0x100000000ull + seg - 1u) / seg);   // i / seg = umulhi(i, seg_inv) for i < 2^16
-    for (uint32_t i = tid; i < 256u * RST; i += LZ2_THREADS) { cntA[i] = 0; cntB[i] = 0; }
+    {   // both sets of counters are zeroed 16 bytes at a time
+        static_assert((256u * RST * sizeof(Cnt)) % 16u == 0, "whole 16-byte stores");
+        uint4 *const zA = reinterpret_cast<uint4 *>(cntA), *const zB = reinterpret_cast<uint4 *>(cntB);
+        for (uint32_t i = tid; i < 256u * RST * (uint32_t)sizeof(Cnt) / 16u; i += LZ2_THREADS) { zA[i] = make_uint4(0, 0, 0, 0); zB[i] = make_uint4(0, 0, 0, 0); }
+    }
 
     bool viol = false;
-    // ---- this part's positions, in time order: picked out of the block's part map (one byte per position, written by the
-    //      partition).  Thread t looks at positions [128 t, 128 t + 128) — eight 16-byte loads — counts the bytes that equal this
-    //      part's number (an exact SWAR zero-byte test per dword), a prefix sum over the threads gives its place, and it writes
-    //      its positions there in ascending order: a stable compaction without a single atomic.  (Round 3 read a list the
-    //      partition had sorted: item -> list -> words was a chain of three dependent global round trips, 26 % of this kernel.)
+    // ---- this part's positions, in time order: picked out of the block's part map — seven bit planes, bit p of plane b = bit b
+    //      of the part of position p (partmap_planes.h, written by the partition).  Thread t looks at positions [128 t, 128 t + 128)
+    //      — one 16-byte load per plane, a wave reads 1 KiB contiguous of each — and a position is this part's where all seven
+    //      bits equal the part number's: at most 13 logic ops per 32 positions (rounds 4 to 19: a byte per position and an exact
+    //      SWAR zero-byte test per dword, ~350 VALU per thread).  A prefix sum over the threads gives its place,
+    //      and it writes its positions there in ascending order: a stable compaction without a single atomic.  (Round 3 read a
+    //      list the partition had sorted: item -> list -> words was a chain of three dependent global round trips, 26 % of this
+    //      kernel.)
     {
-        constexpr uint32_t BPT = LZ_MAX_BLOCK / LZ2_THREADS;                // bytes of the map per thread
-        static_assert(BPT % 16u == 0, "whole 16-byte loads");
-        const uint4 *pm = reinterpret_cast<const uint4 *>(sc.partmap + (size_t)lb * LZ_MAX_BLOCK + (size_t)tid * BPT);
-        static_assert(BPT == 128u, "the match bitmap below is four dwords per thread");
-        const uint32_t pat = part * 0x01010101u;
-        auto nib = [&](uint32_t w) -> uint32_t {                            // bit k set: byte k of w equals `part`
-            const uint32_t x = w ^ pat;
-            const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;      // bit 7 of every zero byte of x, exactly
-            return (((z >> 7) * 0x00204081u) >> 21) & 15u;                  // bits 0, 8, 16, 24 -> 0..3 (the partial products never overlap)
-        };
-        // the loads first, all eight; what stays alive across the prefix sum is one match bit per position: four registers
-        uint32_t bm[4] = {0u, 0u, 0u, 0u};
+        constexpr uint32_t BPT = LZ_MAX_BLOCK / LZ2_THREADS;                // positions per thread
+        static_assert(BPT == 128u, "four dwords of every plane per thread: one 16-byte load each, four match dwords");
+        const uint4 *pm = reinterpret_cast<const uint4 *>(sc.partmap + (size_t)lb * (PMP_BLOCK_BYTES / 4u)) + tid;
+        // the loads first, all seven; what stays alive across the prefix sum is one match bit per position: four registers
+        uint32_t bm[4];
         {
-            uint4 pv[BPT / 16u];
+            uint32_t pl[PMP_PLANES][4];
 #pragma unroll
-            for (uint32_t q = 0; q < BPT / 16u; ++q) pv[q] = pm[q];
-#pragma unroll
-            for (uint32_t q = 0; q < BPT / 16u; ++q)
-                bm[q >> 1] |= (nib(pv[q].x) | (nib(pv[q].y) << 4) | (nib(pv[q].z) << 8) | (nib(pv[q].w) << 12)) << (16u * (q & 1u));
+            for (uint32_t q = 0; q < PMP_PLANES; ++q) {
+                const uint4 v = pm[q * (PMP_PLANE_BYTES / 16u)];
+                pl[q][0] = v.x; pl[q][1] = v.y; pl[q][2] = v.z; pl[q][3] = v.w;
+            }
+            pmp_match_bits(pl, part, bm);
         }
         const uint32_t mine = (uint32_t)(__popc(bm[0]) + __popc(bm[1]) + __popc(bm[2]) + __popc(bm[3]));
         __shared__ uint32_t s_scanp[LZ2_NWAVES + 2];
@@ -1378,7 +1379,7 @@ static uint32_t lz2_class_cap(uint32_t c)
 
 void lz2_carve(mi_carver &cv, uint32_t nb, bool debug, Lz2Scratch *sc)
 {
-    sc->partmap = cv.take<uint8_t>((size_t)nb * LZ_MAX_BLOCK);
+    sc->partmap = cv.take<uint32_t>((size_t)nb * (PMP_BLOCK_BYTES / 4u));
     sc->plist = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
     sc->cand = cv.take<uint16_t>((size_t)nb * LZ_MAX_BLOCK);
     sc->meta = cv.take<Lz2BlockMeta>(nb);
@@ -1435,12 +1436,31 @@ extern "C" int mi_test_prefix_stats(mi_ctx *ctx, uint64_t *out2, int reset)
 }
 #endif
 
+#ifdef MI_TEST_HOOKS
+// lib_test only (tests/test_partmap_planes_gpu.py): the part map and the block records that the context's LAST partition launch
+// wrote (one batch: the caller encodes a small input through any entry point first, which picks the kernel's instance).
+// planes: [max_blocks][PMP_BLOCK_BYTES / 4], meta: [max_blocks] Lz2BlockMeta as dwords.  Returns the launch's blocks (at most
+// max_blocks are copied), or -1 — no launch yet, or a HIP error.
+extern "C" int mi_test_partmap(mi_ctx *ctx, uint32_t *planes, uint32_t *meta, uint32_t max_blocks)
+{
+    if (!ctx || !planes || !meta || !ctx->test_partmap) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    const uint32_t nb = ctx->test_partmap_nb < max_blocks ? ctx->test_partmap_nb : max_blocks;
+    if (hipMemcpy(planes, ctx->test_partmap, (size_t)nb * PMP_BLOCK_BYTES, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(meta, ctx->test_partmap_meta, (size_t)nb * sizeof(Lz2BlockMeta), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (int)ctx->test_partmap_nb;
+}
+#endif
+
 // stage A1: partition (also decides which blocks go to the fallback pipeline)
 mi_status lz2_stage_partition(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint64_t block0, uint32_t nb,
                               const Lz2Scratch &sc, hipStream_t s)
 {
     MI_HIP(ctx, hipMemsetAsync(sc.fallback_count, 0, (64 + 2 * LANE_SIZES) * 4, s));      // fallback_count, big_count[], lane_hist[]
     if (sc.dbg && ctx->lz_dbg != sc.dbg) { ctx->lz_dbg = sc.dbg; MI_HIP(ctx, hipMemsetAsync(sc.dbg, 0, 512, s)); }
+#ifdef MI_TEST_HOOKS
+    ctx->test_partmap = sc.partmap; ctx->test_partmap_meta = sc.meta; ctx->test_partmap_nb = nb;      // (mi_test_partmap)
+#endif
     mi_prof_scope p(ctx, "k_lz2_partition", s, (uint64_t)nb * P.block);
     lz2_launch_partition(d_in, n, P, sc, block0, nb, s);
     MI_HIP(ctx, hipGetLastError());

@@ -161,8 +161,13 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
         };
         // parts of at most LZ2_CAP_S entries (four workgroups of stage 2 per CU); where no certified cut lies that close — one
         // cluster of more entries — a part of up to LZ2_CAP entries (k_lz2_find_wide: two per CU)
-        while (n - cur > LZ2_CAP_S) {
-            int32_t gr = cut_below(cur + LZ2_CAP_S);
+#ifdef MI_TEST_HOOKS                                       /* lib_test only (MI_LZ_TEST_SMALL_PARTS=1): parts of at most 640 entries — a full block of text */
+        const uint32_t cap_s = (P.flags & LZP_SMALL_PARTS) ? 640u : LZ2_CAP_S;   /* gets ~100 of them: the part map's seventh plane, parts beyond stage 2's grid */
+#else
+        constexpr uint32_t cap_s = LZ2_CAP_S;
+#endif
+        while (n - cur > cap_s) {
+            int32_t gr = cut_below(cur + cap_s);
             if (gr < (int32_t)glo) {
                 if (n - cur <= LZ2_CAP) break;                                     // the rest is one wide part
                 gr = cut_below(cur + LZ2_CAP);
@@ -265,20 +270,34 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
         for (uint32_t i = 0; i < 64u; ++i) {
             const uint32_t p = (uint32_t)tid + 1024u * i;
             const uint32_t g = (gcache[i >> 1] >> (16u * (i & 1u))) & 0xFFFFu;
-            part_in[p] = (p < n) ? s_gpart[(g - gstart_) & (LZ2_NG - 1u)] : (uint8_t)0xFF;      // 0xFF: no position (parts are numbered < 128)
+            part_in[p] = (p < n) ? s_gpart[(g - gstart_) & (LZ2_NG - 1u)] : (uint8_t)PMP_NONE;   // no position: the code no part has (lz2.h)
         }
     }
     __syncthreads();
     PT_TICK(5);
-    // The part of every position goes out as it stands, 64 KiB of bytes, coalesced.  Round 3 sorted the positions into
-    // per-part lists here (one stable radix pass over the block: 87 k of this kernel's 205 k cycles — 27 distinct digits, so the
-    // lanes of every counting and ranking atomic pile up on a few LDS addresses — and 128 KiB of scattered 2-byte stores);
-    // now every workgroup of stage 2 picks its own positions out of this map with byte compares and a prefix sum, in time
-    // order by construction (lz2_find.hip).
+    // The part of every position goes out as seven bit planes (partmap_planes.h), 56 KiB, coalesced: every workgroup of stage 2
+    // picks its own positions out of them with a few logic ops per 32 positions and a prefix sum, in time order by construction
+    // (lz2_find.hip).  Round 3 sorted the positions into per-part lists here (one stable radix pass over the block: 87 k of this
+    // kernel's 205 k cycles — 27 distinct digits, so the lanes of every counting and ranking atomic pile up on a few LDS
+    // addresses — and 128 KiB of scattered 2-byte stores); rounds 4 to 19 wrote the map as one byte per position, which each of a
+    // block's ~33 workgroups of stage 2 compared byte by byte.
+    // Every thread transposes 64 consecutive positions; the planes are staged in s_in (dead since the hashing loop: the groups
+    // live in gcache) — not in place, part_in is still being read by other threads.
     {
-        uint4 *dst = reinterpret_cast<uint4 *>(sc.partmap + (size_t)lb * LZ_MAX_BLOCK);
-        const uint4 *srcv = reinterpret_cast<const uint4 *>(part_in);
-        for (uint32_t i = tid; i < LZ_MAX_BLOCK / 16u; i += 1024u) dst[i] = srcv[i];
+        uint32_t *stage = reinterpret_cast<uint32_t *>(s_in);
+        static_assert(sizeof(s_in) >= PMP_BLOCK_BYTES && LZ_MAX_BLOCK == 64u * 1024u, "the planes of a block are staged in s_in, 64 positions per thread");
+        const uint4 *srcv = reinterpret_cast<const uint4 *>(part_in) + 4u * (uint32_t)tid;
+        uint32_t w[16], lo[PMP_PLANES], hi[PMP_PLANES];
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) { const uint4 v = srcv[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+        pmp_planes_of_bytes(w, lo, hi);
+#pragma unroll
+        for (uint32_t b = 0; b < PMP_PLANES; ++b)
+            *reinterpret_cast<uint2 *>(stage + b * (PMP_PLANE_BYTES / 4u) + 2u * (uint32_t)tid) = make_uint2(lo[b], hi[b]);
+        __syncthreads();
+        uint4 *dst = reinterpret_cast<uint4 *>(sc.partmap + (size_t)lb * (PMP_BLOCK_BYTES / 4u));
+        const uint4 *stv = reinterpret_cast<const uint4 *>(stage);
+        for (uint32_t i = tid; i < PMP_BLOCK_BYTES / 16u; i += 1024u) dst[i] = stv[i];
     }
     PT_TICK(6);
     if (sc.dbg && tid == 0) atomicAdd((unsigned long long *)&sc.dbg[47], 1ull);
