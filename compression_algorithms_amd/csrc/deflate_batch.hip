@@ -15,6 +15,8 @@
 //                  record goes to d_out[item] + header + (bytes of the item's earlier records) — dword stores where the
 //                  destination is aligned, bytes at the edges, every store checked against the item's capacity
 //   k_dfb_finish   one wave per item: the checksum from its blocks' parts, container header, 03 00, trailer, size, verdict
+// The batched Snappy encoder (snappy_batch.hip) runs the same frame with its own records: DFB_SNAPPY in DfbCall.container makes the
+// bytes in front of an item's records a function of the item (its preamble) and the finish write that preamble and nothing else.
 //
 // The grid of every pipeline kernel is sized by the caller's bound (no device-to-host read), so blocks between the real count
 // and the bound exist as PAD blocks: one zero byte each, encoded like any one-byte block and placed nowhere.  They do not
@@ -71,8 +73,16 @@ size_t dfb_ws_bytes(const DfbCall &b) { return dfb_carve(nullptr, b).bytes; }
 // one cell per block slot of a scratch set, and room for the 16-byte words the block loaders round their reads out to
 size_t dfb_stage_bytes(const DfbCall &b, uint32_t nbmax, uint32_t block) { return b.ulen ? (size_t)nbmax * block + 64u : 0; }
 
-// the container header's bytes: with a dictionary the zlib header carries DICTID
-static uint32_t dfb_header_bytes(const DfbCall &b) { return defz_header_bytes(b.container) + (b.ulen && b.container == MI_CONTAINER_ZLIB ? 4u : 0u); }
+// the bytes in front of an item's first record.  The three DEFLATE containers: the container header, the same for every item of a
+// call (`uniform`, from the host: with a dictionary the zlib header carries DICTID).  Snappy: the item's preamble, varint32(in_bytes).
+static uint32_t dfb_header_uniform(const DfbCall &b)
+{
+    return b.container == DFB_SNAPPY ? 0u : defz_header_bytes(b.container) + (b.ulen && b.container == MI_CONTAINER_ZLIB ? 4u : 0u);
+}
+__device__ __forceinline__ uint32_t dfb_header_bytes(const DfbCall &b, uint32_t item, uint32_t uniform)
+{
+    return b.container == DFB_SNAPPY ? dfb_varint_bytes(b.in_bytes[item]) : uniform;
+}
 
 struct OpAddU64 { __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; } };
 
@@ -205,7 +215,7 @@ void k_dfb_place(DfbCall b, const LzBlkDesc *__restrict__ desc, const uint32_t *
     }
     // ---- the copy: slot bytes [0, rec) -> out[at, at + rec), nothing at or past the capacity
     uint8_t *out = reinterpret_cast<uint8_t *>(b.out[d.item]);
-    const uint64_t cap = b.out_cap[d.item], at = (uint64_t)hb + before;
+    const uint64_t cap = b.out_cap[d.item], at = (uint64_t)dfb_header_bytes(b, d.item, hb) + before;
     if (at >= cap) return;                                             // (the needed size goes on accumulating above)
     const uint32_t *S = slots + (size_t)lb * LZ_SLOT_WORDS;
     const uint8_t *Sb = reinterpret_cast<const uint8_t *>(S);
@@ -265,6 +275,16 @@ void k_dfb_finish(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_f
     const uint64_t cap = b.out_cap[i];
     auto put = [&](uint64_t at, uint32_t v) { if (at < cap) out[at] = (uint8_t)v; };
     uint64_t r = 0;
+    if (b.container == DFB_SNAPPY) {
+        // the preamble and the records: no closing block, no trailer; an empty item is the single byte 00
+        for (uint64_t v = nb;; v >>= 7) { put(r++, (uint32_t)(v & 0x7Fu) | (v > 0x7Fu ? 0x80u : 0u)); if (v <= 0x7Fu) break; }
+        r += nblk ? item_total[i] : 0ull;
+        const uint32_t st = r <= cap ? MI_OK : MI_ERR_CAPACITY;
+        b.status[i] = st;
+        b.out_bytes[i] = r;
+        if (st != MI_OK && b.failed) atomicAdd(b.failed, 1u);
+        return;
+    }
     if (b.container == MI_CONTAINER_ZLIB && b.ulen) {                 // FDICT, and DICTID: the Adler-32 of the whole dictionary
         const uint32_t id = *dictid;
         put(0, 0x78); put(1, 0xBB); r = 2;
@@ -314,7 +334,7 @@ void dfb_launch_place(const DfbCall &b, void *ws, const uint32_t *slots, const u
 {
     const DfbWs w = dfb_carve(ws, b);
     hipLaunchKernelGGL(k_dfb_place, dim3(nb), dim3(256), 0, s, b, w.desc, w.item_first, w.item_total,
-                       reinterpret_cast<uint64_t *>(w.head + 8), (uint32_t)(seq & 1u), dfb_header_bytes(b), slots, block_bits, b0, nb);
+                       reinterpret_cast<uint64_t *>(w.head + 8), (uint32_t)(seq & 1u), dfb_header_uniform(b), slots, block_bits, b0, nb);
 }
 
 void dfb_launch_stage(const DfbCall &b, uint32_t block, void *ws, uint64_t b0, uint32_t nb, hipStream_t s)

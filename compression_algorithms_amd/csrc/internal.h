@@ -74,11 +74,11 @@ mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint6
 mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
                    void *zws, uint64_t *d_out_bytes, hipStream_t s);
 
-// ---- lz_emit.hip: the encoder pipeline and the form of its output (lz_emit.hip describes the five); deflate_batch.hip: what a batch
+// ---- lz_emit.hip: the encoder pipeline and the form of its output (lz_emit.hip describes the six); deflate_batch.hip: what a batch
 // adds to it — the descriptor table and per-block checksums in front, the placement of one pipeline batch's records, the per-item finish
-enum LzForm { LZ_TOKENS, LZ_H, LZ_Z, LZ_BGZF, LZ_BATCH };
+enum LzForm { LZ_TOKENS, LZ_H, LZ_Z, LZ_BGZF, LZ_BATCH, LZ_SNAPPY };
 struct DfbCall;
-struct LzCall { LzForm form; uint32_t container; uint64_t *d_out_bytes; const DfbCall *batch; };   // container, d_out_bytes: LZ_Z, LZ_BGZF; batch: LZ_BATCH
+struct LzCall { LzForm form; uint32_t container; uint64_t *d_out_bytes; const DfbCall *batch; };   // container, d_out_bytes: LZ_Z, LZ_BGZF; batch: LZ_BATCH, LZ_SNAPPY
 mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
                          uint64_t *d_block_bits, void *stream, const LzCall &c);
 struct DfbCall {
@@ -100,6 +100,10 @@ __host__ __device__ static inline uint64_t dfb_nblk(uint64_t nb, uint32_t block,
 }
 __host__ __device__ static inline uint64_t dfb_begin_of(uint64_t k, uint32_t block, uint32_t ulen) { return k ? (uint64_t)(block - ulen) + (k - 1u) * block : 0; }
 #define DFB_MAX_BYTES 0x7FFFFFFFull            // per item and per count: block numbers and positions inside an item are 32-bit
+// DfbCall.container of LZ_SNAPPY (snappy_batch.hip): not a public container — every public entry point refuses a value above
+// MI_CONTAINER_GZIP.  An item is its preamble, varint32(in_bytes), then its blocks' records: no 03 00, no trailer, no checksum.
+#define DFB_SNAPPY    0x100u
+__host__ __device__ static inline uint32_t dfb_varint_bytes(uint64_t v) { uint32_t k = 1; while (v >>= 7) ++k; return k; }
 size_t    dfb_ws_bytes(const DfbCall &b);
 mi_status dfb_begin(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s, const uint8_t **desc);
 void      dfb_launch_place(const DfbCall &b, void *ws, const uint32_t *slots, const uint64_t *block_bits, uint64_t b0, uint32_t nb,
@@ -108,6 +112,10 @@ mi_status dfb_end(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipSt
 void      dfb_launch_stage(const DfbCall &b, uint32_t block, void *ws, uint64_t b0, uint32_t nb, hipStream_t s);   // U and the items' heads -> the cells
 uint32_t  dfb_ulen(uint64_t dict_bytes, uint32_t block);                                                           // |U| = min(dict_bytes, 32 768, block / 2)
 size_t    dfb_stage_bytes(const DfbCall &b, uint32_t nbmax, uint32_t block);                                       // per scratch set; 0 without a dictionary
+
+// ---- snappy_batch.hip: the last stage of LZ_SNAPPY — one raw Snappy record per block in its slot, block_bits[lb] = 8 x its bytes
+void      snappy_launch_emit(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_desc, uint32_t block,
+                             uint64_t b0, uint32_t nb, hipStream_t s);
 
 // ---- inflate_batch.hip: the per-item limit
 #define INFB_MAX_BYTES 0x7FFFFFFFull           // per item, compressed and inflated: positions inside an item are 32-bit

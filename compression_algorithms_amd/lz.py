@@ -17,7 +17,8 @@ from .context import as_device_bytes, default_context
 
 def params(flavour="deflate", wbits=None, block=65536, parse=0):
     """parse: 0 the reference's greedy parse; 1 the lazy parse with matches up to 255 bytes, for the standard-DEFLATE writers
-    only (compress_z, compress_bgzf, deflate_batch and their host forms; include/mi_codec.h, mode Z)"""
+    only (compress_z, compress_bgzf, deflate_batch and their host forms; include/mi_codec.h, mode Z) and for
+    snappy_compress_batch, which runs the same pipeline"""
     if flavour == "deflate":
         return _lib.LzParams(15, 5, 20, 1, block, parse)
     if flavour == "lz77":
@@ -988,4 +989,159 @@ def deflate_batch_host(items, p=None, container="gzip", ctx=None, zdict=None):
         st = ctx.L.mi_deflate_batch_dict(ctx.h, C.byref(p), c, count, h_in, h_nb, h_out, h_cap, sizes, status,
                                          hd.ctypes.data_as(C.c_void_p) if hd.size else None, hd.size)
     _lib.check(st, "mi_deflate_batch")
+    return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]
+
+
+# ---- batched Snappy: many independent RAW Snappy buffers (what snappy.compress / pyarrow's "snappy" codec write) per call ---------
+class SnappyBatch(InflateBatch):
+    """The result of snappy_compress_batch / snappy_decompress_batch, shaped like InflateBatch and DeflateBatch: `outputs` (a
+    list of uint8 device tensors, each cut to its size; empty where the item failed), `out_bytes` (int64; the size needed where
+    the status is MI_ERR_CAPACITY) and `status` (int32) device tensors, `failed` (how many items are not MI_OK)."""
+
+    def raise_for_status(self):
+        if self.failed:
+            st = [int(v) for v in self.status.cpu()]
+            i = next(k for k, v in enumerate(st) if v)
+            raise _lib.MiError(st[i], f"snappy batch: {self.failed} of {len(st)} items failed, the first one item {i}")
+        return self
+
+
+def snappy_batch_bound_bytes(n, p=None):
+    """mi_snappy_batch_bound_bytes: the most an item of n bytes comes to"""
+    p = p or params("deflate")
+    return int(_lib.lib().mi_snappy_batch_bound_bytes(n, C.byref(p)))
+
+
+def _batch_outputs(ctx, cap, count):
+    """one packed output for the capacities -> (buffer, its offsets, device tensors of pointers and capacities)"""
+    d_cap = torch.tensor(cap, dtype=torch.int64, device=ctx.device) if count else torch.zeros(0, dtype=torch.int64, device=ctx.device)
+    at, offs = 0, []
+    for v in cap:
+        offs.append(at)
+        at += (min(v, 0x7FFFFFFF) + 15) & ~15                 # (a capacity above that is refused per item)
+    out = torch.empty(max(at, 16), dtype=torch.uint8, device=ctx.device)
+    d_out = torch.tensor([out.data_ptr() + a for a in offs], dtype=torch.int64, device=ctx.device) if count else d_cap
+    return out, offs, d_out, d_cap
+
+
+def _snappy_sizes_dev(ctx, count, d_in, d_nb):
+    sizes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    st = ctx.L.mi_snappy_batch_size_dev(ctx.h, count, _ptr(d_in), _ptr(d_nb), _ptr(sizes), _ptr(status), None, ctx.stream_ptr())
+    _lib.check(st, "mi_snappy_batch_size_dev")
+    return sizes[:count], status[:count]
+
+
+def snappy_batch_sizes(items, ctx=None):
+    """The preamble of every item (what snappy's GetUncompressedLength answers) -> (sizes int64, status int32) device tensors.
+    `items` as for snappy_decompress_batch.  The body is not validated: an item that is MI_OK here may still be corrupt."""
+    off, count = _batch_check(items, None)
+    ctx = ctx or default_context()
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    out = _snappy_sizes_dev(ctx, count, d_in, d_nb)
+    ctx.sync()                                                 # (the inputs in `keep` may go now)
+    return out
+
+
+def snappy_decompress_batch(items, caps=None, ctx=None):
+    """Decode many independent raw Snappy buffers in one launch -> SnappyBatch.
+
+    items: a list of bytes or uint8 tensors, or a pair (buffer, offsets) for a packed buffer with count + 1 offsets (item i is
+    buffer[offsets[i]:offsets[i + 1]]: no alignment needed).  caps: the output capacity of every item (list or tensor); None
+    reads the preambles first and allocates one packed output.  An item whose preamble exceeds its capacity comes back
+    MI_ERR_CAPACITY with out_bytes = the preamble and nothing written; a malformed one MI_ERR_CORRUPT; one bad item does not
+    spoil the rest.  Raw Snappy only: not the framing format (.sz), not Hadoop's block wrapper."""
+    off, count = _batch_check(items, caps)
+    ctx = ctx or default_context()
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    if caps is None:
+        cap = [int(v) for v in _snappy_sizes_dev(ctx, count, d_in, d_nb)[0].cpu()]
+    else:
+        cap = [int(v) for v in (caps.cpu().tolist() if torch.is_tensor(caps) else caps)]
+    out, offs, d_out, d_cap = _batch_outputs(ctx, cap, count)
+    nbytes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+    st = ctx.L.mi_snappy_decode_batch_dev(ctx.h, count, _ptr(d_in), _ptr(d_nb), _ptr(d_out), _ptr(d_cap), _ptr(nbytes), _ptr(status),
+                                          _ptr(failed), 0, ctx.stream_ptr())
+    _lib.check(st, "mi_snappy_decode_batch_dev")
+    ctx.sync()
+    nb, stl = [int(v) for v in nbytes[:count].cpu()], [int(v) for v in status[:count].cpu()]
+    outputs = [out[a:a + (n if s == 0 else 0)] for a, n, s in zip(offs, nb, stl)]
+    return SnappyBatch(outputs, nbytes[:count], status[:count], int(failed.item()) if count else 0)
+
+
+def snappy_compress_batch(items, p=None, caps=None, ctx=None, max_blocks=None):
+    """Compress many independent buffers in one call, each to a raw Snappy buffer that stock Snappy reads -> SnappyBatch.
+
+    items: as for snappy_decompress_batch.  p: params("deflate", block=..., parse=0 or 1) — the batched deflate's finder, parse
+    and blocks; the format is chosen by this entry point, not by a parameter.  caps: the output capacity of every item; None
+    gives each item its bound in one packed output.  An item that does not fit its capacity comes back MI_ERR_CAPACITY with
+    out_bytes = the size it needs.  max_blocks: the launch bound (None: from the sizes, which are known here)."""
+    off, count = _batch_check(items, caps)
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    sizes = [int(v) for v in d_nb.cpu()] if count else []
+    if caps is None:
+        cap = [snappy_batch_bound_bytes(n, p) for n in sizes]
+    else:
+        cap = [int(v) for v in (caps.cpu().tolist() if torch.is_tensor(caps) else caps)]
+    out, offs, d_out, d_cap = _batch_outputs(ctx, cap, count)
+    if max_blocks is None:
+        max_blocks = sum((n + p.block - 1) // p.block for n in sizes if n <= 0x7FFFFFFF)
+    nbytes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+    v0 = ctx.order_violations()
+    st = ctx.L.mi_snappy_encode_batch_dev(ctx.h, C.byref(p), count, _ptr(d_in), _ptr(d_nb), max_blocks, _ptr(d_out), _ptr(d_cap),
+                                          _ptr(nbytes), _ptr(status), _ptr(failed), ctx.stream_ptr())
+    _lib.check(st, "mi_snappy_encode_batch_dev")
+    ctx.sync()
+    if ctx.order_violations() != v0:
+        raise _lib.MiError(10, "the encoder that wrote this batch reported a sort out of order")
+    nb, stl = [int(v) for v in nbytes[:count].cpu()], [int(v) for v in status[:count].cpu()]
+    outputs = [out[a:a + (n if s == 0 else 0)] for a, n, s in zip(offs, nb, stl)]
+    return SnappyBatch(outputs, nbytes[:count], status[:count], int(failed.item()) if count else 0)
+
+
+def _host_arrays(items):
+    arrs = [np.frombuffer(b, dtype=np.uint8) for b in items]
+    count = len(arrs)
+    h_in = (C.c_void_p * max(count, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    h_nb = (C.c_uint64 * max(count, 1))(*[a.size for a in arrs])
+    return arrs, h_in, h_nb, (C.c_uint64 * max(count, 1))(), (C.c_uint32 * max(count, 1))()
+
+
+def snappy_compress_batch_host(items, p=None, ctx=None):
+    """the host-buffer entry point (mi_snappy_encode_batch): a list of bytes -> (list of bytes, None where the item failed; list
+    of status codes)"""
+    items = [bytes(x) for x in items]
+    count = len(items)
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    arrs, h_in, h_nb, sizes, status = _host_arrays(items)
+    caps = [snappy_batch_bound_bytes(a.size, p) for a in arrs]
+    outs = [np.zeros(max(v, 1), dtype=np.uint8) for v in caps]
+    h_out = (C.c_void_p * max(count, 1))(*[o.ctypes.data for o in outs])
+    h_cap = (C.c_uint64 * max(count, 1))(*caps)
+    st = ctx.L.mi_snappy_encode_batch(ctx.h, C.byref(p), count, h_in, h_nb, h_out, h_cap, sizes, status)
+    _lib.check(st, "mi_snappy_encode_batch")
+    return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]
+
+
+def snappy_decompress_batch_host(items, ctx=None):
+    """the host-buffer entry point (mi_snappy_decode_batch, called once for the preambles and once to decode, so the inputs travel
+    to the device twice: a convenience path): a list of bytes -> (list of bytes, None where the item failed; list of status codes)"""
+    items = [bytes(x) for x in items]
+    count = len(items)
+    ctx = ctx or default_context()
+    arrs, h_in, h_nb, sizes, status = _host_arrays(items)
+    st = ctx.L.mi_snappy_decode_batch(ctx.h, count, h_in, h_nb, None, None, sizes, status, 0)
+    _lib.check(st, "mi_snappy_decode_batch")
+    outs = [np.zeros(max(int(sizes[i]), 1), dtype=np.uint8) for i in range(count)]
+    h_out = (C.c_void_p * max(count, 1))(*[o.ctypes.data for o in outs])
+    h_cap = (C.c_uint64 * max(count, 1))(*[int(sizes[i]) for i in range(count)])
+    st = ctx.L.mi_snappy_decode_batch(ctx.h, count, h_in, h_nb, h_out, h_cap, sizes, status, 0)
+    _lib.check(st, "mi_snappy_decode_batch")
     return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]

@@ -737,6 +737,74 @@ mi_status mi_deflate_batch_dict(mi_ctx *ctx, const mi_lz_params *p, uint32_t con
                                 const uint8_t *h_dict, uint64_t dict_bytes);
 
 /* ------------------------------------------------------------------------------------
+ * Batched Snappy: many independent RAW Snappy buffers encoded or decoded in one call — the
+ * default codec of Parquet pages, offered by ORC, Arrow IPC, Kafka and LevelDB too.  An item is
+ * what snappy::Compress writes and snappy::Uncompress reads (format_description.txt of
+ * google/snappy): varint32(uncompressed length), then literal elements (tag 00) and copies with
+ * a 1-, 2- or 4-byte offset (tags 01, 10, 11).  OUT OF SCOPE: the framing format (.sz files, with
+ * CRC-32C), Hadoop's block wrapper, and reading Parquet page headers (thrift) — the caller hands
+ * over the compressed bytes of each page.
+ * All arrays are DEVICE arrays of `count` entries, as for the batched inflate and deflate above:
+ * items and outputs at any byte address, every item with its own verdict and size, *d_failed (may
+ * be NULL) = the items that are not MI_OK, count == 0 is MI_OK and launches nothing, no item
+ * influences another.  All three device calls are asynchronous on `stream`: no host
+ * synchronisation, no device-to-host read.
+ *
+ * mi_snappy_decode_batch_dev — one wave per item.  flags must be 0.  Loads stay inside the aligned
+ * dwords that cover the item; no byte at or past min(d_out_cap[i], preamble) is stored.
+ *   MI_OK            d_out_bytes[i] = the preamble = the bytes written.
+ *   MI_ERR_CAPACITY  the preamble is larger than d_out_cap[i]: d_out_bytes[i] = the preamble, and
+ *                    NOTHING is written (it is decided before the first store; the body is not
+ *                    validated).
+ *   MI_ERR_CORRUPT   d_out_bytes[i] = 0, bytes below min(capacity, preamble) unspecified: an item
+ *                    of 0 bytes; a preamble that is cut off, longer than five bytes or above
+ *                    2^32 - 1; a copy with offset 0 or an offset larger than the bytes produced so
+ *                    far; an element that would pass the preamble length; input that ends inside
+ *                    an element, or with fewer bytes produced than the preamble says; input left
+ *                    over once the preamble length is reached.
+ *   MI_ERR_ARG       d_out_bytes[i] = 0: a NULL pointer with a non-zero size or capacity; a size,
+ *                    capacity or preamble above 2^31 - 1.
+ * mi_snappy_batch_size_dev — the preamble alone (snappy::GetUncompressedLength), one thread per
+ * item: d_out_bytes[i] and the header verdicts above.  It does NOT validate the body: an item
+ * that is MI_OK here may be MI_ERR_CORRUPT when decoded.
+ *
+ * mi_snappy_encode_batch_dev — the batched deflate's pipeline (same finder, same parse, the same
+ * blocks: stock Snappy also compresses in independent blocks of at most 64 KiB) with Snappy
+ * elements as its last stage.  p and max_blocks: exactly as for mi_deflate_batch_dev (the deflate
+ * flavour, wbits <= 15, block <= 65536, parse 0 or 1; mi_snappy_batch_max_blocks is that call's
+ * rule).  The bytes are deterministic.  Per block, over the token sequence: literals and matches
+ * shorter than 4 gather in a run; a match (L >= 4, d) first flushes the run as ONE literal
+ * element in its shortest form, then becomes copies of 64 while L >= 68, one of 60 if L > 64, and
+ * the rest (so every piece is >= 4), each with a 1-byte offset form when 4 <= len <= 11 and
+ * d < 2048, else the 2-byte form; the run pending at the block's end is flushed.  The 4-byte
+ * offset form is never written.  An empty item is the single byte 00.
+ *   MI_OK / MI_ERR_CAPACITY (d_out_bytes[i] = the exact size needed, nothing written at or past the
+ *   capacity) / MI_ERR_ARG (also: blocks beyond max_blocks) as for mi_deflate_batch_dev.
+ * mi_snappy_batch_bound_bytes(n, p) = 5 + n + n / 61 + 3 ceil(n / block): the preamble; a run of r
+ * literals in front of a copy costs at most r / 61 bytes more than the input it covers together
+ * with that copy; a block's last run at most 3.
+ * The host forms: arrays of host pointers — copy up, run, copy down the items that came out MI_OK;
+ * mi_snappy_decode_batch with h_out = NULL or h_out_cap = NULL answers the sizes alone.
+ * ------------------------------------------------------------------------------------ */
+uint64_t  mi_snappy_batch_bound_bytes(uint64_t n_item, const mi_lz_params *p);
+uint64_t  mi_snappy_batch_max_blocks(uint64_t total_in_bytes, uint64_t count, const mi_lz_params *p);   /* total / block + count */
+mi_status mi_snappy_encode_batch_dev(mi_ctx *ctx, const mi_lz_params *p, uint64_t count,
+                                     const void *const *d_in, const uint64_t *d_in_bytes, uint64_t max_blocks,
+                                     void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                                     uint32_t *d_status, uint32_t *d_failed, void *stream);
+mi_status mi_snappy_decode_batch_dev(mi_ctx *ctx, uint64_t count, const void *const *d_in, const uint64_t *d_in_bytes,
+                                     void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                                     uint32_t *d_status, uint32_t *d_failed, uint32_t flags, void *stream);
+mi_status mi_snappy_batch_size_dev(mi_ctx *ctx, uint64_t count, const void *const *d_in, const uint64_t *d_in_bytes,
+                                   uint64_t *d_out_bytes, uint32_t *d_status, uint32_t *d_failed, void *stream);
+mi_status mi_snappy_encode_batch(mi_ctx *ctx, const mi_lz_params *p, uint64_t count,
+                                 const void *const *h_in, const uint64_t *h_in_bytes,
+                                 void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status);
+mi_status mi_snappy_decode_batch(mi_ctx *ctx, uint64_t count, const void *const *h_in, const uint64_t *h_in_bytes,
+                                 void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status,
+                                 uint32_t flags);
+
+/* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is
  * defined by this build).  Record layout in include/mi_fse.h.
  * ------------------------------------------------------------------------------------ */
