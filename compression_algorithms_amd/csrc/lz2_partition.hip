@@ -23,47 +23,37 @@
 // (internal linkage, as the kernel had before it was a template: the LDS arrays of a template with external linkage are
 //  linkonce symbols the optimiser must keep whole — s_pstart, written and never read, came back as 520 bytes of LDS)
 namespace {
-template <bool DESC>                                 // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
-__global__ __launch_bounds__(1024)
-void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t s_in[LZ_MAX_BLOCK + LZ_TAIL + 16];
-    __shared__ uint32_t s_grp[LZ2_NG];               // counts -> inclusive prefix; later the staging area
-    __shared__ uint32_t s_safe[LZ2_NG / 32];
-    __shared__ uint64_t s_scan64[18];
-    __shared__ uint32_t s_scan32[18];
-    __shared__ uint32_t s_thr[LZ2_MAXPARTS + 1];     // part k = home' in [s_thr[k], s_thr[k+1])
-    __shared__ uint32_t s_pstart[LZ2_MAXPARTS + 1];
-    __shared__ uint32_t s_s0, s_flag;
-
-    const int tid = threadIdx.x;
-    const uint32_t lb = blockIdx.x;
-    long long tk = clock64();
 #define PT_TICK(k) do { if (sc.dbg && tid == 0) { long long t2 = clock64(); atomicAdd((unsigned long long *)&sc.dbg[32 + (k)], (unsigned long long)(t2 - tk)); tk = t2; } } while (0)
-    const uint8_t *src; uint32_t n;
-    lz_block_src<DESC>(in, n_total, P.block, block0, lb, src, n);
-    const uint32_t T = 1u << P.tbits, Tmask = T - 1u;
-    const uint32_t gshift = P.tbits - LZ2_NG_BITS, Gw = 1u << gshift;
 
-    lz_block_to_lds_of<DESC>(s_in, src, n, (uint32_t)tid);
-    for (uint32_t i = tid; i < LZ2_NG; i += 1024) s_grp[i] = 0;
-    for (uint32_t i = tid; i < LZ2_NG / 32; i += 1024) s_safe[i] = 0;
-    if (tid == 0) { s_s0 = ~0u; s_flag = 0; }
-    __syncthreads();
-    auto home_of = [&](uint32_t p) -> uint32_t { return lz_mix32(lds_word(s_in, p)) & Tmask; };
-    PT_TICK(0);
-    // the group of every position stays in registers (two 14-bit numbers per register, 64 positions per thread): the hash is
-    // computed once — the pass that tabulates the part of every position further down used to compute it again
-    uint32_t gcache[32];
-#pragma unroll
-    for (uint32_t i = 0; i < 64u; ++i) {
-        const uint32_t p = (uint32_t)tid + 1024u * i;
-        uint32_t g = 0;
-        if (p < n) { g = home_of(p) >> gshift; atomicAdd(&s_grp[g], 1u); }
-        if (i & 1u) gcache[i >> 1] |= g << 16; else gcache[i >> 1] = g;
-    }
-    __syncthreads();
-    PT_TICK(1);
+// The LDS of a partition kernel, as the part of the kernel that both of them share takes it.  (The kernels declare the
+// arrays: the one that keeps the block in registers lays s_gpart over s_grp, the other has room for both.)
+struct Lz2PartLds {
+    uint32_t *s_grp;                                 // [LZ2_NG] entries per group on entry; the inclusive prefix from then on
+    uint32_t *s_safe;                                // [LZ2_NG / 32] certified groups, zero on entry
+    uint64_t *s_scan64;                              // [18]
+    uint32_t *s_scan32;                              // [18]
+    uint32_t *s_thr;                                 // [LZ2_MAXPARTS + 1] part k = home' in [s_thr[k], s_thr[k+1])
+    uint32_t *s_pstart;                              // [LZ2_MAXPARTS + 1]
+    uint8_t  *s_gpart;                               // [LZ2_NG] out: part of every rotated group.  May lie over s_grp: its first writer is
+                                                     // two barriers behind the last reader of the prefix
+    uint8_t  *s_wrank;                               // [LZ2_MAXPARTS]
+    uint32_t *s_s0, *s_flag;                         // one word each: the first certified group (~0u on entry), "fall back" (0 on entry)
+    uint32_t *s_K, *s_wbase, *s_wbase2;              // one word each
+};
+
+// From the counts per group to the part of every group: the overflow certificate, the cuts, the block's record, its parts on
+// the work list (or the block on the fallback list) and the table s_gpart.  Called by all 1024 threads behind the barrier that
+// ends the counting; returns behind the barrier that ends the tabulation, with the first group of the rotated order in `gstart`
+// — or false, with no barrier pending, where the block goes to the fallback pipeline.
+__device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const LzP &P, const Lz2Scratch &sc, uint32_t lb, uint32_t n, int tid, long long &tk,
+                                                   uint32_t &gstart_out)
+{
+    uint32_t *const s_grp = L.s_grp, *const s_safe = L.s_safe, *const s_scan32 = L.s_scan32, *const s_thr = L.s_thr, *const s_pstart = L.s_pstart;
+    uint64_t *const s_scan64 = L.s_scan64;
+    uint8_t *const s_gpart = L.s_gpart, *const s_wrank = L.s_wrank;
+    uint32_t &s_s0 = *L.s_s0, &s_flag = *L.s_flag, &s_K = *L.s_K, &s_wbase = *L.s_wbase, &s_wbase2 = *L.s_wbase2;
+    const uint32_t T = 1u << P.tbits;
+    const uint32_t gshift = P.tbits - LZ2_NG_BITS, Gw = 1u << gshift;
 
     // ---- overflow certificate: 16 consecutive groups per thread
     const uint32_t g0 = tid * (LZ2_NG / 1024);
@@ -126,8 +116,7 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     // a block holds one cluster larger than the margin — measured: target 3072 gave +5 % on one corpus and a 6x collapse
     // (every block in the fallback) on another seed whose text has a 1000-entry cluster — while greedy parts only fail when
     // a single cluster exceeds LZ2_CAP.  The cuts depend on each other, so one wave walks them (<= 32 64-way searches).
-    __shared__ uint32_t s_K;
-    if (tid < 64) {                                     // wave 0, every lane with the same cur / glo / k
+    if (tid < 64) {                                    // wave 0, every lane with the same cur / glo / k
         const uint32_t lane = (uint32_t)tid;
         uint32_t k = 0, cur = 0, glo = 0;               // parts so far, entries before the current part, its first rotated group
         bool bad = false;
@@ -219,14 +208,12 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     }
     if (s_flag != 0 || (P.deflate && no_safe)) {
         if (tid == 0 && P.stats) atomicAdd((unsigned long long *)&P.stats[0], 1ull);      // mi_lz_path_stats: blocks sent to the fallback
-        return;
+        return false;
     }
     // this block's parts join the batch's work list: stage 2 runs one workgroup per LISTED part.  (A grid of
     // blocks x "most parts a block can have" interleaved a third of empty workgroups with the real ones; each still had to
     // be given stage 2's 67 KiB of LDS before it could leave: 14.65 -> 11.4 GB/s.)
     {
-        __shared__ uint32_t s_wbase, s_wbase2;
-        __shared__ uint8_t s_wrank[LZ2_MAXPARTS];
         if (tid == 0) {
             uint32_t ns = 0, nw = 0;
             for (uint32_t k = 0; k < K; ++k) s_wrank[k] = (uint8_t)(mt->part_count[k] <= LZ2_CAP_S ? ns++ : nw++);
@@ -242,13 +229,8 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
         }
     }
 
-    // ---- positions -> part lists, time order kept: ONE stable radix pass over the whole block by part number.  The part of
-    //      every position is tabulated first (one hash per position), the pass then stores straight to the block's list in
-    //      HBM: consecutive positions of one part land on consecutive addresses, and the exclusive scan over the parts is
-    //      exactly the list layout (part k starts at the number of entries in parts < k).  (Staging 8192 positions at a
-    //      time through LDS paid the pass's fixed costs eight times: 7.5 -> see DESIGN.md for the measurement.)
-    uint8_t  *part_in = reinterpret_cast<uint8_t *>(s_grp);             // [65536] part of every position; the group array is dead now
-    __shared__ __attribute__((aligned(16))) uint8_t s_gpart[LZ2_NG];   // part of every rotated group (part boundaries are group boundaries)
+    // ---- the part of every rotated group (part boundaries are group boundaries): what the kernels look the part of a position
+    //      up in.  (s_grp is dead here: its last reader, cum_incl of the part sizes, is two barriers back.)
     {
         // sixteen consecutive groups per thread: one binary search for the first, then a walk along the thresholds
         constexpr uint32_t GPT = LZ2_NG / 1024;
@@ -264,8 +246,59 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     }
     __syncthreads();
     PT_TICK(4);
+    gstart_out = gstart;                                // the ring is cut on a group boundary
+    return true;
+}
+
+template <bool DESC>                                 // DESC: `in` is the batched encoder's descriptor table (lz_block_src)
+__global__ __launch_bounds__(1024)
+void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[LZ_MAX_BLOCK + LZ_TAIL + 16];
+    __shared__ uint32_t s_grp[LZ2_NG];               // counts -> inclusive prefix; later the staging area
+    __shared__ uint32_t s_safe[LZ2_NG / 32];
+    __shared__ uint64_t s_scan64[18];
+    __shared__ uint32_t s_scan32[18];
+    __shared__ uint32_t s_thr[LZ2_MAXPARTS + 1];
+    __shared__ uint32_t s_pstart[LZ2_MAXPARTS + 1];
+    __shared__ uint32_t s_s0, s_flag, s_K, s_wbase, s_wbase2;
+    __shared__ uint8_t s_wrank[LZ2_MAXPARTS];
+    __shared__ __attribute__((aligned(16))) uint8_t s_gpart[LZ2_NG];
+
+    const int tid = threadIdx.x;
+    const uint32_t lb = blockIdx.x;
+    long long tk = clock64();
+    const uint8_t *src; uint32_t n;
+    lz_block_src<DESC>(in, n_total, P.block, block0, lb, src, n);
+    const uint32_t T = 1u << P.tbits, Tmask = T - 1u;
+    const uint32_t gshift = P.tbits - LZ2_NG_BITS;
+
+    lz_block_to_lds_of<DESC>(s_in, src, n, (uint32_t)tid);
+    for (uint32_t i = tid; i < LZ2_NG; i += 1024) s_grp[i] = 0;
+    for (uint32_t i = tid; i < LZ2_NG / 32; i += 1024) s_safe[i] = 0;
+    if (tid == 0) { s_s0 = ~0u; s_flag = 0; }
+    __syncthreads();
+    auto home_of = [&](uint32_t p) -> uint32_t { return lz_mix32(lds_word(s_in, p)) & Tmask; };
+    PT_TICK(0);
+    // the group of every position stays in registers (two 14-bit numbers per register, 64 positions per thread): the hash is
+    // computed once — the pass that tabulates the part of every position further down used to compute it again
+    uint32_t gcache[32];
+#pragma unroll
+    for (uint32_t i = 0; i < 64u; ++i) {
+        const uint32_t p = (uint32_t)tid + 1024u * i;
+        uint32_t g = 0;
+        if (p < n) { g = home_of(p) >> gshift; atomicAdd(&s_grp[g], 1u); }
+        if (i & 1u) gcache[i >> 1] |= g << 16; else gcache[i >> 1] = g;
+    }
+    __syncthreads();
+    PT_TICK(1);
+
+    uint32_t gstart_;
+    if (!lz2_partition_cuts(Lz2PartLds{s_grp, s_safe, s_scan64, s_scan32, s_thr, s_pstart, s_gpart, s_wrank, &s_s0, &s_flag, &s_K, &s_wbase, &s_wbase2}, P, sc, lb, n, tid, tk, gstart_)) return;
+
+    // ---- positions -> the part map.  The part of every position is tabulated first, one byte each, from the groups in gcache.
+    uint8_t *part_in = reinterpret_cast<uint8_t *>(s_grp);              // [65536] part of every position; the group array is dead now
     {
-        const uint32_t gstart_ = base >> gshift;        // the ring is cut on a group boundary
 #pragma unroll
         for (uint32_t i = 0; i < 64u; ++i) {
             const uint32_t p = (uint32_t)tid + 1024u * i;
@@ -302,11 +335,123 @@ void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz
     PT_TICK(6);
     if (sc.dbg && tid == 0) atomicAdd((unsigned long long *)&sc.dbg[47], 1ull);
 }
+
+// The same for blocks of ONE buffer that start on 16-byte boundaries (lz2_launch_partition picks), with the block kept in
+// registers: thread t owns the positions [64 t, 64 t + 64) from the loads to the stores.  Their 64 words come out of the 17
+// dwords that hold the bytes [64 t, 64 t + 68) with one v_alignbyte each, the groups stay in registers as above, and so do the part
+// bytes, which the same thread transposes: it holds dwords 2 t and 2 t + 1 of every plane, and a wave stores 512 contiguous bytes
+// of a plane with one 8-byte store per lane.  No copy of the block, no byte per position and no staged planes in LDS: 68 KiB
+// instead of 147, two workgroups per CU.
+// The phase counters keep their numbers: 0 ends behind the zeroing of the counts (the loads are still in flight: their wait is
+// in phase 1), 5 is the part of every own position and the transposition, 6 the stores.
+__global__ __launch_bounds__(1024, 8)
+void k_lz2_partition_direct(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_grp[LZ2_NG];   // counts -> inclusive prefix -> (as bytes) the part of every group
+    __shared__ uint32_t s_safe[LZ2_NG / 32];
+    __shared__ uint64_t s_scan64[18];
+    __shared__ uint32_t s_scan32[18];
+    __shared__ uint32_t s_thr[LZ2_MAXPARTS + 1];
+    __shared__ uint32_t s_pstart[LZ2_MAXPARTS + 1];
+    __shared__ uint32_t s_s0, s_flag, s_K, s_wbase, s_wbase2;
+    __shared__ uint8_t s_wrank[LZ2_MAXPARTS];
+    static_assert(LZ_MAX_BLOCK == 64u * 1024u, "64 positions per thread");
+
+    const int tid = threadIdx.x;
+    const uint32_t lb = blockIdx.x;
+    long long tk = clock64();
+    const uint8_t *src; uint32_t n;
+    lz_block_src<false>(in, n_total, P.block, block0, lb, src, n);
+    const uint32_t Tmask = (1u << P.tbits) - 1u;
+    const uint32_t gshift = P.tbits - LZ2_NG_BITS;
+    const uint32_t p0 = 64u * (uint32_t)tid;
+
+    // The bytes [p0, p0 + 68): four 16-byte words and the first dword of a fifth, issued together.  As in lz_load16_pair, only
+    // aligned 16-byte words that hold a byte of the block are read (an offset past the last of them is clamped to it: the
+    // loads stay unconditional), and bytes at or past n count as zero — the reference's over-read (lz_block_to_lds).
+    uint32_t w[17];
+    {
+        const uint32_t last = n ? (n - 1u) & ~15u : 0u;
+        uint4 v[4] = {};
+        uint32_t v4 = 0u;
+        if (n) {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) { const uint32_t o = p0 + 16u * k; v[k] = *reinterpret_cast<const uint4 *>(src + (o <= last ? o : last)); }
+            v4 = *reinterpret_cast<const uint32_t *>(src + (p0 + 64u <= last ? p0 + 64u : last));
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) { w[4 * k] = v[k].x; w[4 * k + 1] = v[k].y; w[4 * k + 2] = v[k].z; w[4 * k + 3] = v[k].w; }
+        w[16] = v4;
+    }
+    for (uint32_t i = tid; i < LZ2_NG; i += 1024) s_grp[i] = 0;
+    for (uint32_t i = tid; i < LZ2_NG / 32; i += 1024) s_safe[i] = 0;
+    if (tid == 0) { s_s0 = ~0u; s_flag = 0; }
+    __syncthreads();
+    PT_TICK(0);
+    if (p0 + 68u > n) {                              // the thread the block ends in, and the ones behind it
+#pragma unroll
+        for (uint32_t j = 0; j < 17u; ++j) {
+            const uint32_t o = p0 + 4u * j, keep = n > o ? n - o : 0u;          // bytes of this dword below n
+            if (keep < 4u) w[j] &= keep ? (1u << (8u * keep)) - 1u : 0u;
+        }
+    }
+    // the group of own position p0 + i (below n): its word is one v_alignbyte of two of the 17 dwords
+    auto group_of = [&](uint32_t i) -> uint32_t {
+        const uint32_t word = (i & 3u) ? __builtin_amdgcn_alignbyte(w[(i >> 2) + 1], w[i >> 2], i & 3u) : w[i >> 2];
+        return (lz_mix32(word) & Tmask) >> gshift;
+    };
+    // the group of every own position, two per register, as in k_lz2_partition.  (Keeping the 17 dwords instead and hashing a
+    // second time below — 48 VGPRs, not 62 — was measured: 2.36 against 1.89 ms of partition per step)
+    uint32_t gcache[32];
+    // No branch per position: the thread the block ends in adds 0 for its positions at or past n, the threads behind it skip
+    // the loop.  Eight positions at a time — all 64 hashes in flight at once do not fit 64 VGPRs.
+    if (p0 < n) {
+#pragma unroll
+        for (uint32_t i = 0; i < 64u; ++i) {
+            const uint32_t g = group_of(i);
+            atomicAdd(&s_grp[g], p0 + i < n ? 1u : 0u);
+            if (i & 1u) gcache[i >> 1] |= g << 16; else gcache[i >> 1] = g;
+            if ((i & 7u) == 7u) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    __syncthreads();
+    PT_TICK(1);
+
+    uint8_t *s_gpart = reinterpret_cast<uint8_t *>(s_grp);
+    uint32_t gstart_;
+    if (!lz2_partition_cuts(Lz2PartLds{s_grp, s_safe, s_scan64, s_scan32, s_thr, s_pstart, s_gpart, s_wrank, &s_s0, &s_flag, &s_K, &s_wbase, &s_wbase2}, P, sc, lb, n, tid, tk, gstart_)) return;
+
+    uint32_t pb[16], lo[PMP_PLANES], hi[PMP_PLANES];   // the part of every own position, four per register, then their planes
+#pragma unroll
+    for (uint32_t q = 0; q < 16u; ++q) pb[q] = PMP_NONE * 0x01010101u;          // no position: the code no part has (lz2.h)
+    if (p0 < n) {
+#pragma unroll
+        for (uint32_t i = 0; i < 64u; ++i) {
+            const uint32_t g = (gcache[i >> 1] >> (16u * (i & 1u))) & 0xFFFFu;
+            const uint32_t look = s_gpart[(g - gstart_) & (LZ2_NG - 1u)], part = (p0 + i < n) ? look : PMP_NONE;
+            if (i & 3u) pb[i >> 2] |= part << (8u * (i & 3u)); else pb[i >> 2] = part;
+            if ((i & 7u) == 7u) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    pmp_planes_of_bytes(pb, lo, hi);
+    PT_TICK(5);
+    uint2 *dst = reinterpret_cast<uint2 *>(sc.partmap + (size_t)lb * (PMP_BLOCK_BYTES / 4u)) + tid;
+#pragma unroll
+    for (uint32_t b = 0; b < PMP_PLANES; ++b) dst[b * (PMP_PLANE_BYTES / 8u)] = make_uint2(lo[b], hi[b]);
+    PT_TICK(6);
+    if (sc.dbg && tid == 0) atomicAdd((unsigned long long *)&sc.dbg[47], 1ull);
+}
 }  // namespace
 
 void lz2_launch_partition(const uint8_t *d_in, uint64_t n, const LzP &P, const Lz2Scratch &sc, uint64_t block0, uint32_t nb, hipStream_t s)
 {
+    // one buffer whose blocks all start on 16-byte boundaries: the kernel that keeps the block in registers
+    bool direct = !(P.flags & LZP_DESC) && (((uintptr_t)d_in) & 15u) == 0 && P.block % 16u == 0 && P.block <= LZ_MAX_BLOCK;
+#ifdef MI_TEST_HOOKS                                       /* lib_test only (MI_LZ_TEST_OLD_PARTITION=1): such input through k_lz2_partition<false> too, */
+    if (P.flags & LZP_OLD_PARTITION) direct = false;       /* so that a test can compare what the two kernels write (tests/test_partition_direct_gpu.py) */
+#endif
     if (P.flags & LZP_DESC) hipLaunchKernelGGL(k_lz2_partition<true>, dim3(nb), dim3(1024), 0, s, d_in, n, P, sc, block0);
+    else if (direct) hipLaunchKernelGGL(k_lz2_partition_direct, dim3(nb), dim3(1024), 0, s, d_in, n, P, sc, block0);
     else hipLaunchKernelGGL(k_lz2_partition<false>, dim3(nb), dim3(1024), 0, s, d_in, n, P, sc, block0);
 }
 

@@ -47,5 +47,7 @@ pp = v[32:39]
 nb_ = max(v[47], 1)
 if v[47]:
     print("k_lz2_partition blocks:", int(v[47]), " cycles/block:", int(pp.sum() / nb_))
-    for k, nm in enumerate(["load", "hash+count", "certificate+prefix", "cuts", "part table", "part of every position", "radix pass"]):
+    # (k_lz2_partition_direct: "load" ends with its loads still in flight — their wait is in "hash+count" —, and the part of every
+    #  position includes the transposition: its "planes + copy out" is the stores alone)
+    for k, nm in enumerate(["load", "hash+count", "certificate+prefix", "cuts", "part table", "part of every position", "planes + copy out"]):
         print(f"  {nm:24s} {100 * pp[k] / pp.sum():5.1f} %   {pp[k] / nb_:9.0f} cycles/block")
