@@ -42,6 +42,7 @@ struct mi_ctx {
     int         test_force_fb = 0;     // MI_LZ_TEST_FORCE_FALLBACK=1 (lib_test only): every block goes to the fallback pipeline
     int         test_small_parts = 0;  // MI_LZ_TEST_SMALL_PARTS=1 (lib_test only): parts of at most 640 entries (lz2_partition.hip)
     int         test_old_partition = 0; // MI_LZ_TEST_OLD_PARTITION=1 (lib_test only): aligned one-buffer input through k_lz2_partition too
+    int         test_old_cuts = 0;     // MI_LZ_TEST_OLD_CUTS=1 (lib_test only): the partition's cut walk searches as it did before the window (lz2_partition.hip)
     uint64_t   *d_stats = nullptr;     // device counters behind mi_lz_path_stats: [0] fallback blocks, [1] wide parts
     uint32_t   *h_order = nullptr;     // pinned, device-visible: set by a kernel that found a sort out of order (lz_common.h)
     uint32_t   *d_order = nullptr;     // the same word as the device addresses it

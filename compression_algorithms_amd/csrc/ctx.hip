@@ -114,6 +114,7 @@ mi_status mi_ctx_create(mi_ctx **out, int device)
     c->test_force_fb = getenv("MI_LZ_TEST_FORCE_FALLBACK") != nullptr;       // (only a -DMI_TEST_HOOKS build looks at the flag)
     c->test_small_parts = getenv("MI_LZ_TEST_SMALL_PARTS") != nullptr;       // (likewise)
     c->test_old_partition = getenv("MI_LZ_TEST_OLD_PARTITION") != nullptr;   // (likewise)
+    c->test_old_cuts = getenv("MI_LZ_TEST_OLD_CUTS") != nullptr;             // (likewise)
     if (hipMalloc((void **)&c->d_stats, 64) != hipSuccess || hipMemset(c->d_stats, 0, 64) != hipSuccess) { mi_ctx_destroy(c); return MI_ERR_NOMEM; }
     *out = c;
     return MI_OK;

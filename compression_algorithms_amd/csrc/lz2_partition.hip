@@ -55,10 +55,12 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
     const uint32_t T = 1u << P.tbits;
     const uint32_t gshift = P.tbits - LZ2_NG_BITS, Gw = 1u << gshift;
 
+    constexpr uint32_t GPT = LZ2_NG / 1024;            // groups per thread
+    static_assert(GPT == 16u, "a thread's part bytes are one 16-byte word");
     // ---- overflow certificate: 16 consecutive groups per thread
-    const uint32_t g0 = tid * (LZ2_NG / 1024);
+    const uint32_t g0 = tid * GPT;
     AffMax mine{0, AM_NEG};
-    for (uint32_t k = 0; k < LZ2_NG / 1024; ++k) {
+    for (uint32_t k = 0; k < GPT; ++k) {
         const int32_t c = (int32_t)s_grp[g0 + k];
         mine = am_then(mine, AffMax{c - (int32_t)Gw, c > 0 ? c - 1 : 0});
     }
@@ -71,7 +73,7 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
         int32_t x = x0 + pre.a > pre.b ? x0 + pre.a : pre.b;
         if (x < 0) x = 0;
         uint32_t safe_bits = 0;
-        for (uint32_t k = 0; k < LZ2_NG / 1024; ++k) {
+        for (uint32_t k = 0; k < GPT; ++k) {
             const int32_t c = (int32_t)s_grp[g0 + k];
             int32_t o = x + c - (int32_t)Gw;
             const int32_t o2 = c > 0 ? c - 1 : 0;
@@ -87,24 +89,25 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
     // inclusive prefix of counts, in place
     {
         uint32_t sum = 0;
-        for (uint32_t k = 0; k < LZ2_NG / 1024; ++k) sum += s_grp[g0 + k];
+        for (uint32_t k = 0; k < GPT; ++k) sum += s_grp[g0 + k];
         uint32_t tot;
         uint32_t run = block_exclusive_scan<uint32_t>(sum, OpAddU32(), 0u, s_scan32, &tot);
-        for (uint32_t k = 0; k < LZ2_NG / 1024; ++k) { run += s_grp[g0 + k]; s_grp[g0 + k] = run; }
+        for (uint32_t k = 0; k < GPT; ++k) { run += s_grp[g0 + k]; s_grp[g0 + k] = run; }
     }
     __syncthreads();
 
     PT_TICK(2);
     // ---- cut the ring / choose the parts
     Lz2BlockMeta *mt = sc.meta + lb;
-    const uint32_t s0 = s_s0;
+    const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_s0);        // (the same for every lane: kept in a scalar register)
     const bool no_safe = (s0 == ~0u);
     // rotated group order starts after s0 (deflate) or at group 0 (lz77: nothing wraps into bucket 0)
     const uint32_t gstart = P.deflate ? (no_safe ? 0u : ((s0 + 1u) & (LZ2_NG - 1u))) : 0u;
     const uint32_t base = gstart << gshift;
+    // entries in front of the rotated order: read once, not with every count, and kept in a scalar register
+    const uint32_t before = gstart ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s_grp[gstart - 1]) : 0u;
     auto cum_incl = [&](uint32_t gr) -> uint32_t {      // entries in rotated groups 0..gr
         const uint32_t g = (gstart + gr) & (LZ2_NG - 1u);
-        const uint32_t before = gstart ? s_grp[gstart - 1] : 0u;
         return g >= gstart ? s_grp[g] - before : s_grp[g] + (n - before);
     };
     auto is_safe = [&](uint32_t gr) -> bool {
@@ -115,18 +118,62 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
     // that fits.  A fixed target with a fixed margin (parts of TS + "how far back the cut had to move") fails as soon as
     // a block holds one cluster larger than the margin — measured: target 3072 gave +5 % on one corpus and a 6x collapse
     // (every block in the fallback) on another seed whose text has a 1000-entry cluster — while greedy parts only fail when
-    // a single cluster exceeds LZ2_CAP.  The cuts depend on each other, so one wave walks them (<= 32 64-way searches).
+    // a single cluster exceeds LZ2_CAP.  The cuts depend on each other, so one wave walks them.
+    // The walking wave issues ahead of the CU's other waves: fifteen of its own workgroup wait at the barrier below, but the second
+    // workgroup on the CU is hashing, and a lone wave of normal priority gets its turn among that one's four on its SIMD.  (The
+    // guard is a scalar branch: s_setprio ignores EXEC, so under `tid < 64` alone every wave would raise its priority.)
+    const bool walker = __builtin_amdgcn_readfirstlane(tid) < 64;
+    if (walker) __builtin_amdgcn_s_setprio(3);
     if (tid < 64) {                                    // wave 0, every lane with the same cur / glo / k
         const uint32_t lane = (uint32_t)tid;
         uint32_t k = 0, cur = 0, glo = 0;               // parts so far, entries before the current part, its first rotated group
         bool bad = false;
         if (lane == 0) s_thr[0] = 0;
-        // last certified group g in [glo, .) with at most `limit` entries in rotated groups 0..g, or -1
-        auto cut_below = [&](uint32_t limit) -> int32_t {
-            // (a part of a 2^20-bucket table is also kept below 2^16 homes: stage 2 then sorts 16-bit keys in two radix
-            //  passes instead of three; a 2^22-bucket table spreads 4096 entries over ~2^18 homes whatever the cut)
-            const uint32_t span = (gshift <= 6u) ? (65536u >> gshift) : LZ2_NG;
-            // first rotated group in [glo, hi) whose inclusive count exceeds the limit, else hi: a 64-way search
+        // (a part of a 2^20-bucket table is also kept below 2^16 homes: stage 2 then sorts 16-bit keys in two radix
+        //  passes instead of three; a 2^22-bucket table spreads 4096 entries over ~2^18 homes whatever the cut)
+        const uint32_t span = (gshift <= 6u) ? (65536u >> gshift) : LZ2_NG;
+        // Last certified group g in [glo, .) with at most `limit` entries in rotated groups 0..g, or -1; `upto` gets that count.
+        // The boundary is the first rotated group in [glo, hi) whose inclusive count exceeds the limit, else hi.  A cut costs ONE
+        // dependent LDS round trip.  The wave keeps 256 checkpoints in registers, four per lane: the count at the end of every
+        // 64th group, read once per walk.  How many of them lie within the limit (four ballots) names the 64 groups that hold
+        // the first group above it; those 64 groups — or the 64 in front of hi, where hi comes first — are then looked at
+        // together, count and certificate bit of a lane's group in one trip: the last certified group lies 0 groups below the
+        // boundary in the median and within 10 on text.  Until round 23: two 64-way probes through LDS, a look
+        // back and the count, five trips; a first form of the window behind one probe through LDS: two trips, measured slower.
+        uint32_t cp[4];                                 // checkpoint lane + 64 q: the entries in rotated groups 0 .. 64 (lane + 64 q) + 63
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) cp[q] = cum_incl(64u * (lane + 64u * q) + 63u);
+        auto cut_below = [&](uint32_t limit, uint32_t &upto) -> int32_t {
+            // how many of the 256 checkpoints lie within the limit: the first group above it is in the 64 behind them
+            uint32_t j = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < 4u; ++q) j += (uint32_t)__popcll(__ballot(cp[q] <= limit));
+            const uint32_t hi0 = (glo + span < LZ2_NG) ? glo + span : LZ2_NG - 1, hi = hi0 < 64u * j + 64u ? hi0 : 64u * j + 64u;
+            // the window [hi - 64, hi), lanes below glo off: counts grow with the group, so the first lane over the limit is the
+            // boundary (no lane: hi itself) and every group in front of the window is under the limit
+            const int32_t w0 = (int32_t)hi - 64, c = w0 + (int32_t)lane;
+            const bool on = c >= (int32_t)glo;
+            const uint32_t g = (gstart + (uint32_t)c) & (LZ2_NG - 1u);
+            uint32_t cum = 0u, sw = 0u;
+            if (on) { cum = s_grp[g]; sw = s_safe[g >> 5]; }
+            cum = g >= gstart ? cum - before : cum + (n - before);
+            const uint64_t mo = __ballot(on && cum > limit);
+            const uint64_t ms = __ballot(on && ((sw >> (g & 31u)) & 1u)) & (mo ? (1ull << __builtin_ctzll(mo)) - 1ull : ~0ull);
+            if (ms) {
+                const uint32_t l = 63u - (uint32_t)__builtin_clzll(ms);
+                upto = (uint32_t)__builtin_amdgcn_readlane((int)cum, (int)l);
+                return w0 + (int32_t)l;
+            }
+            // no certified group in the window below the boundary (never on text): further back, 64 groups per look
+            for (int32_t gb = w0 - 1; gb >= (int32_t)glo; gb -= 64) {
+                const int32_t cb = gb - (int32_t)lane;
+                const uint64_t mk = __ballot(cb >= (int32_t)glo && is_safe((uint32_t)cb));
+                if (mk) { const int32_t gr = gb - (int32_t)__builtin_ctzll(mk); upto = cum_incl((uint32_t)gr); return gr; }
+            }
+            return -1;
+        };
+#ifdef MI_TEST_HOOKS                                       /* lib_test only (MI_LZ_TEST_OLD_CUTS=1): the search as it was, so that a test can compare the */
+        auto cut_below_old = [&](uint32_t limit, uint32_t &upto) -> int32_t {        /* parts of both (tests/test_partition_cuts_gpu.py) */
             uint32_t lo = glo, hi = (glo + span < LZ2_NG) ? glo + span : LZ2_NG - 1;
             while (lo < hi) {
                 const uint32_t len = hi - lo, step = (len + 63u) / 64u;
@@ -144,10 +191,15 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
             for (int32_t g = (int32_t)lo - 1; g >= (int32_t)glo; g -= 64) {
                 const int32_t c = g - (int32_t)lane;
                 const uint64_t mk = __ballot(c >= (int32_t)glo && is_safe((uint32_t)c));
-                if (mk) return g - (int32_t)__builtin_ctzll(mk);
+                if (mk) { const int32_t gr = g - (int32_t)__builtin_ctzll(mk); upto = cum_incl((uint32_t)gr); return gr; }
             }
             return -1;
         };
+        const bool old_cuts = (P.flags & LZP_OLD_CUTS) != 0u;
+        auto cut = [&](uint32_t limit, uint32_t &upto) -> int32_t { return old_cuts ? cut_below_old(limit, upto) : cut_below(limit, upto); };
+#else
+        auto cut = cut_below;
+#endif
         // parts of at most LZ2_CAP_S entries (four workgroups of stage 2 per CU); where no certified cut lies that close — one
         // cluster of more entries — a part of up to LZ2_CAP entries (k_lz2_find_wide: two per CU)
 #ifdef MI_TEST_HOOKS                                       /* lib_test only (MI_LZ_TEST_SMALL_PARTS=1): parts of at most 640 entries — a full block of text */
@@ -156,15 +208,16 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
         constexpr uint32_t cap_s = LZ2_CAP_S;
 #endif
         while (n - cur > cap_s) {
-            int32_t gr = cut_below(cur + cap_s);
+            uint32_t upto = 0u;                                                    // entries in rotated groups 0..gr
+            int32_t gr = cut(cur + cap_s, upto);
             if (gr < (int32_t)glo) {
                 if (n - cur <= LZ2_CAP) break;                                     // the rest is one wide part
-                gr = cut_below(cur + LZ2_CAP);
+                gr = cut(cur + LZ2_CAP, upto);
             }
             // no certified cut within LZ2_CAP entries: one cluster larger than stage 2 can hold.  (k + 2 > LZ2_MAXPARTS cannot
             // happen — the static_assert in lz2.h has the argument — and stays as a guard.)
             if (gr < (int32_t)glo || k + 2 > LZ2_MAXPARTS) { bad = true; break; }
-            cur = cum_incl((uint32_t)gr);
+            cur = upto;
             glo = (uint32_t)gr + 1u;
             ++k;
             if (lane == 0) s_thr[k] = glo << gshift;
@@ -178,6 +231,7 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
             if (bad) s_flag = 1;
         }
     }
+    if (walker) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
     const uint32_t K = s_K;                             // <= LZ2_MAXPARTS
     PT_TICK(3);
@@ -233,16 +287,18 @@ __device__ __forceinline__ bool lz2_partition_cuts(const Lz2PartLds &L, const Lz
     //      up in.  (s_grp is dead here: its last reader, cum_incl of the part sizes, is two barriers back.)
     {
         // sixteen consecutive groups per thread: one binary search for the first, then a walk along the thresholds
-        constexpr uint32_t GPT = LZ2_NG / 1024;
         const uint32_t gr0 = (uint32_t)tid * GPT;
         uint32_t lo = 0, hi = K - 1;                    // last k with thr[k] <= h
         { const uint32_t h = gr0 << gshift; while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (s_thr[mid] <= h) lo = mid; else hi = mid - 1; } }
         uint32_t nxt = lo + 1 < K ? s_thr[lo + 1] : 0xFFFFFFFFu;
+        uint32_t pk[GPT / 4u];                          // the sixteen part bytes: one 16-byte store (s_gpart is 16-byte aligned in both kernels)
+#pragma unroll
         for (uint32_t k = 0; k < GPT; ++k) {
             const uint32_t h = (gr0 + k) << gshift;
             while (h >= nxt) { ++lo; nxt = lo + 1 < K ? s_thr[lo + 1] : 0xFFFFFFFFu; }
-            s_gpart[gr0 + k] = (uint8_t)lo;
+            if (k & 3u) pk[k >> 2] |= lo << (8u * (k & 3u)); else pk[k >> 2] = lo;
         }
+        *reinterpret_cast<uint4 *>(s_gpart + gr0) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
     }
     __syncthreads();
     PT_TICK(4);
@@ -255,7 +311,7 @@ __global__ __launch_bounds__(1024)
 void k_lz2_partition(const uint8_t *__restrict__ in, uint64_t n_total, LzP P, Lz2Scratch sc, uint64_t block0)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_in[LZ_MAX_BLOCK + LZ_TAIL + 16];
-    __shared__ uint32_t s_grp[LZ2_NG];               // counts -> inclusive prefix; later the staging area
+    __shared__ __attribute__((aligned(16))) uint32_t s_grp[LZ2_NG];   // counts -> inclusive prefix (read and written 16 bytes at a time); later the staging area
     __shared__ uint32_t s_safe[LZ2_NG / 32];
     __shared__ uint64_t s_scan64[18];
     __shared__ uint32_t s_scan32[18];

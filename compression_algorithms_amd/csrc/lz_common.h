@@ -41,6 +41,7 @@ struct LzP {
 #define LZP_LAZY 16u       // mi_lz_params.parse == MI_PARSE_LAZY (mode Z's forms only, defz_check): stage C launches the parse-1 k_lz_parse_emit
 #define LZP_SMALL_PARTS 32u // TEST BUILD ONLY (-DMI_TEST_HOOKS, MI_LZ_TEST_SMALL_PARTS=1): the partition aims for parts of 640 entries, not LZ2_CAP_S
 #define LZP_OLD_PARTITION 64u // TEST BUILD ONLY (-DMI_TEST_HOOKS, MI_LZ_TEST_OLD_PARTITION=1): aligned one-buffer input goes through k_lz2_partition too
+#define LZP_OLD_CUTS 128u  // TEST BUILD ONLY (-DMI_TEST_HOOKS, MI_LZ_TEST_OLD_CUTS=1): the cut walk finds each cut with the search it had before the 64-group window
 
 // The stable radix scatter under LZP_ARANK ranks by the order in which ONE returning LDS add serves the lanes that hit one
 // address — lane order on gfx950, measured (scripts/micro/lds_atomic_order.hip) and probed once per context (ctx.hip), but
@@ -63,6 +64,7 @@ static inline LzP lz_params_of(mi_ctx *ctx, const mi_lz_params *p)
     if (ctx->test_force_fb) fl |= LZP_FORCE_FB;
     if (ctx->test_small_parts) fl |= LZP_SMALL_PARTS;
     if (ctx->test_old_partition) fl |= LZP_OLD_PARTITION;
+    if (ctx->test_old_cuts) fl |= LZP_OLD_CUTS;
     if (p->parse == MI_PARSE_LAZY) fl |= LZP_LAZY;
     return LzP{p->wbits, p->lbits, p->tbits, p->deflate, p->block, fl, ctx->d_order, ctx->d_stats};
 }
