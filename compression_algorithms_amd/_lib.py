@@ -65,6 +65,8 @@ EXPORTS = [
     "mi_deflate_batch_dict_bound_bytes", "mi_deflate_batch_dict_max_blocks", "mi_deflate_batch_dict_dev", "mi_deflate_batch_dict",
     "mi_snappy_batch_bound_bytes", "mi_snappy_batch_max_blocks", "mi_snappy_encode_batch_dev", "mi_snappy_decode_batch_dev",
     "mi_snappy_batch_size_dev", "mi_snappy_encode_batch", "mi_snappy_decode_batch",
+    "mi_lz4_batch_bound_bytes", "mi_lz4_batch_max_blocks", "mi_lz4_encode_batch_dev", "mi_lz4_decode_batch_dev",
+    "mi_lz4_batch_size_dev", "mi_lz4_encode_batch", "mi_lz4_decode_batch",
     "mi_bgzf_bound_bytes", "mi_bgzf_encode_dev", "mi_bgzf_encode", "mi_bgzf_index_dev", "mi_bgzf_inflate_dev", "mi_bgzf_inflate",
     "mi_bgzf_read_max_pieces", "mi_bgzf_read_ranges_dev", "mi_bgzf_read_ranges",
     "mi_fse_block_bound", "mi_fse_encode_dev", "mi_fse_decode_dev", "mi_fse_encode", "mi_fse_decode", "mi_fse_normalise_dev",
@@ -188,6 +190,17 @@ def lib():
             L.mi_snappy_batch_size_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
             L.mi_snappy_encode_batch.argtypes = [vp, C.POINTER(LzParams), u64, vp, vp, vp, vp, vp, vp]
             L.mi_snappy_decode_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, u32]
+        if hasattr(L, "mi_lz4_decode_batch_dev"):
+            u32 = C.c_uint32
+            L.mi_lz4_batch_bound_bytes.restype = u64
+            L.mi_lz4_batch_bound_bytes.argtypes = [u64, C.POINTER(LzParams), u32]
+            L.mi_lz4_batch_max_blocks.restype = u64
+            L.mi_lz4_batch_max_blocks.argtypes = [u64, u64, C.POINTER(LzParams)]
+            L.mi_lz4_encode_batch_dev.argtypes = [vp, C.POINTER(LzParams), u32, u64, vp, vp, u64, vp, vp, vp, vp, vp, vp]
+            L.mi_lz4_decode_batch_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp]
+            L.mi_lz4_batch_size_dev.argtypes = [vp, u64, vp, vp, vp, vp, vp, u32, vp]
+            L.mi_lz4_encode_batch.argtypes = [vp, C.POINTER(LzParams), u32, u64, vp, vp, vp, vp, vp, vp]
+            L.mi_lz4_decode_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, u32, u32]
         if hasattr(L, "mi_bgzf_encode_dev"):
             u32 = C.c_uint32
             L.mi_bgzf_bound_bytes.restype = u64

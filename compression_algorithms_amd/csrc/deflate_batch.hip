@@ -17,6 +17,8 @@
 //   k_dfb_finish   one wave per item: the checksum from its blocks' parts, container header, 03 00, trailer, size, verdict
 // The batched Snappy encoder (snappy_batch.hip) runs the same frame with its own records: DFB_SNAPPY in DfbCall.container makes the
 // bytes in front of an item's records a function of the item (its preamble) and the finish write that preamble and nothing else.
+// The batched LZ4 encoder (lz4_batch.hip) likewise: DFB_LZ4_BLOCK has no header and refuses an item of more than one block in the
+// scan; DFB_LZ4_FRAME has a uniform 7-byte header and the finish writes it and the EndMark.
 //
 // The grid of every pipeline kernel is sized by the caller's bound (no device-to-host read), so blocks between the real count
 // and the bound exist as PAD blocks: one zero byte each, encoded like any one-byte block and placed nowhere.  They do not
@@ -75,8 +77,10 @@ size_t dfb_stage_bytes(const DfbCall &b, uint32_t nbmax, uint32_t block) { retur
 
 // the bytes in front of an item's first record.  The three DEFLATE containers: the container header, the same for every item of a
 // call (`uniform`, from the host: with a dictionary the zlib header carries DICTID).  Snappy: the item's preamble, varint32(in_bytes).
+// LZ4: uniform too — nothing in front of a raw block, the frame header's seven bytes.
 static uint32_t dfb_header_uniform(const DfbCall &b)
 {
+    if (b.container == DFB_LZ4_BLOCK || b.container == DFB_LZ4_FRAME) return b.container == DFB_LZ4_FRAME ? 7u : 0u;
     return b.container == DFB_SNAPPY ? 0u : defz_header_bytes(b.container) + (b.ulen && b.container == MI_CONTAINER_ZLIB ? 4u : 0u);
 }
 __device__ __forceinline__ uint32_t dfb_header_bytes(const DfbCall &b, uint32_t item, uint32_t uniform)
@@ -102,6 +106,7 @@ void k_dfb_scan(DfbCall b, uint32_t block, uint32_t *__restrict__ item_first, ui
         if (i < count) {
             const uint64_t nb = b.in_bytes[i], cap = b.out_cap[i];
             if ((nb && !b.in[i]) || (cap && !b.out[i]) || nb > DFB_MAX_BYTES || cap > DFB_MAX_BYTES) st = MI_ERR_ARG;
+            else if (b.container == DFB_LZ4_BLOCK && nb > block) st = MI_ERR_ARG;      // a raw LZ4 item is one block: refused alone, with 0 blocks
             else nblk = dfb_nblk(nb, block, b.ulen);
         }
         uint64_t tot;
@@ -234,6 +239,8 @@ void k_dfb_place(DfbCall b, const LzBlkDesc *__restrict__ desc, const uint32_t *
     if (t0 + tid < rec && at + t0 + tid < cap) out[at + t0 + tid] = Sb[t0 + tid];     // (at most three bytes)
 }
 
+__constant__ uint8_t kDfbLz4Frame[7] = {0x04, 0x22, 0x4D, 0x18, 0x60, 0x40, 0x82};   // version 1, independent blocks, no checksums, no content
+                                                                                     // size, 64 KiB maximum; HC = byte 1 of XXH32(60 40)
 __constant__ uint8_t kDfbGzip[10] = {0x1F, 0x8B, 0x08, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0xFF};    // as k_defz_finish writes it
 
 __global__ __launch_bounds__(64)
@@ -279,6 +286,19 @@ void k_dfb_finish(DfbCall b, uint32_t block, const uint32_t *__restrict__ item_f
         // the preamble and the records: no closing block, no trailer; an empty item is the single byte 00
         for (uint64_t v = nb;; v >>= 7) { put(r++, (uint32_t)(v & 0x7Fu) | (v > 0x7Fu ? 0x80u : 0u)); if (v <= 0x7Fu) break; }
         r += nblk ? item_total[i] : 0ull;
+        const uint32_t st = r <= cap ? MI_OK : MI_ERR_CAPACITY;
+        b.status[i] = st;
+        b.out_bytes[i] = r;
+        if (st != MI_OK && b.failed) atomicAdd(b.failed, 1u);
+        return;
+    }
+    if (b.container == DFB_LZ4_BLOCK || b.container == DFB_LZ4_FRAME) {
+        // a raw block: its one record, or the closing token 00 alone for an empty item; a frame: header, the blocks' slots, EndMark
+        const bool fr = b.container == DFB_LZ4_FRAME;
+        if (fr) for (uint32_t k = 0; k < 7u; ++k) put(r++, kDfbLz4Frame[k]);
+        r += nblk ? item_total[i] : 0ull;
+        if (fr) for (uint32_t k = 0; k < 4u; ++k) put(r++, 0u);
+        else if (!nblk) put(r++, 0u);
         const uint32_t st = r <= cap ? MI_OK : MI_ERR_CAPACITY;
         b.status[i] = st;
         b.out_bytes[i] = r;

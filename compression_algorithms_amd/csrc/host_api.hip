@@ -788,6 +788,45 @@ extern "C" mi_status mi_snappy_decode_batch(mi_ctx *ctx, uint64_t count, const v
                          : mi_snappy_batch_size_dev(ctx, count, d_in, d_in_bytes, d_out_bytes, d_status, nullptr, s); });
 }
 
+// LZ4, raw blocks or frames: as the two Snappy forms (a raw-block item above the block size is refused on the device and has no blocks)
+extern "C" mi_status mi_lz4_encode_batch(mi_ctx *ctx, const mi_lz_params *p, uint32_t format, uint64_t count, const void *const *h_in,
+                                         const uint64_t *h_in_bytes, void *const *h_out, const uint64_t *h_out_cap,
+                                         uint64_t *h_out_bytes, uint32_t *h_status)
+{
+    if (!ctx || format > MI_LZ4_FRAME) return MI_ERR_ARG;
+    mi_status st = defz_check(p, MI_CONTAINER_RAW);
+    if (st) return st;
+    if (count > DFB_MAX_BYTES) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_in || !h_in_bytes || !h_out || !h_out_cap || !h_out_bytes || !h_status) return MI_ERR_ARG;
+    const BatchItems b{count, h_in, h_in_bytes, h_out, h_out_cap, DFB_MAX_BYTES};
+    return host_encode_with_retry(ctx, [&]() -> mi_status {
+        uint64_t max_blocks = 0;
+        for (uint64_t i = 0; i < count; ++i)
+            if (b.in_ok(i) && (format == MI_LZ4_FRAME || h_in_bytes[i] <= p->block)) max_blocks += (h_in_bytes[i] + p->block - 1) / p->block;
+        if (max_blocks > DFB_MAX_BYTES) return MI_ERR_ARG;
+        return batch_host_once(ctx, b, h_out_bytes, h_status,
+            [&](const void *const *d_in, const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                uint32_t *d_status, hipStream_t s) {
+                return mi_lz4_encode_batch_dev(ctx, p, format, count, d_in, d_in_bytes, max_blocks, d_out, d_out_cap, d_out_bytes, d_status, nullptr, s); });
+    });
+}
+
+extern "C" mi_status mi_lz4_decode_batch(mi_ctx *ctx, uint64_t count, const void *const *h_in, const uint64_t *h_in_bytes,
+                                         void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status,
+                                         uint32_t format, uint32_t flags)
+{
+    if (!ctx || format > MI_LZ4_FRAME || flags || count > 0x7FFFFFFFull) return MI_ERR_ARG;
+    if (count == 0) return MI_OK;
+    if (!h_in || !h_in_bytes || !h_out_bytes || !h_status) return MI_ERR_ARG;
+    const BatchItems b{count, h_in, h_in_bytes, h_out, h_out_cap, INFB_MAX_BYTES};
+    return batch_host_once(ctx, b, h_out_bytes, h_status,
+        [&](const void *const *d_in, const uint64_t *d_in_bytes, void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+            uint32_t *d_status, hipStream_t s) {
+            return d_out ? mi_lz4_decode_batch_dev(ctx, count, d_in, d_in_bytes, d_out, d_out_cap, d_out_bytes, d_status, nullptr, format, flags, s)
+                         : mi_lz4_batch_size_dev(ctx, count, d_in, d_in_bytes, d_out_bytes, d_status, nullptr, format, s); });
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // BGZF read from host bytes: the stream goes up and is indexed on the device in two steps — count the members (and the bytes
 // they inflate to), then, with a table of that size, list them.

@@ -74,11 +74,11 @@ mi_status defz_begin(mi_ctx *ctx, uint32_t container, const uint8_t *d_in, uint6
 mi_status defz_end(mi_ctx *ctx, uint32_t container, uint8_t *d_out, uint64_t *d_block_bits, uint64_t nblocks, uint64_t n,
                    void *zws, uint64_t *d_out_bytes, hipStream_t s);
 
-// ---- lz_emit.hip: the encoder pipeline and the form of its output (lz_emit.hip describes the six); deflate_batch.hip: what a batch
+// ---- lz_emit.hip: the encoder pipeline and the form of its output (lz_emit.hip describes the seven); deflate_batch.hip: what a batch
 // adds to it — the descriptor table and per-block checksums in front, the placement of one pipeline batch's records, the per-item finish
-enum LzForm { LZ_TOKENS, LZ_H, LZ_Z, LZ_BGZF, LZ_BATCH, LZ_SNAPPY };
+enum LzForm { LZ_TOKENS, LZ_H, LZ_Z, LZ_BGZF, LZ_BATCH, LZ_SNAPPY, LZ_LZ4 };
 struct DfbCall;
-struct LzCall { LzForm form; uint32_t container; uint64_t *d_out_bytes; const DfbCall *batch; };   // container, d_out_bytes: LZ_Z, LZ_BGZF; batch: LZ_BATCH, LZ_SNAPPY
+struct LzCall { LzForm form; uint32_t container; uint64_t *d_out_bytes; const DfbCall *batch; };   // container, d_out_bytes: LZ_Z, LZ_BGZF; batch: LZ_BATCH, LZ_SNAPPY, LZ_LZ4
 mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
                          uint64_t *d_block_bits, void *stream, const LzCall &c);
 struct DfbCall {
@@ -104,6 +104,11 @@ __host__ __device__ static inline uint64_t dfb_begin_of(uint64_t k, uint32_t blo
 // MI_CONTAINER_GZIP.  An item is its preamble, varint32(in_bytes), then its blocks' records: no 03 00, no trailer, no checksum.
 #define DFB_SNAPPY    0x100u
 __host__ __device__ static inline uint32_t dfb_varint_bytes(uint64_t v) { uint32_t k = 1; while (v >>= 7) ++k; return k; }
+// DfbCall.container of LZ_LZ4 (lz4_batch.hip), as little public.  DFB_LZ4_BLOCK: an item is ONE block's record and nothing else (an
+// item above the block size is MI_ERR_ARG, an empty one the byte 00).  DFB_LZ4_FRAME: the seven bytes of kDfbLz4Frame, every block's
+// slot (size word and record, or size word and the block stored), the EndMark 00 00 00 00.
+#define DFB_LZ4_BLOCK 0x101u
+#define DFB_LZ4_FRAME 0x102u
 size_t    dfb_ws_bytes(const DfbCall &b);
 mi_status dfb_begin(mi_ctx *ctx, const DfbCall &b, uint32_t block, void *ws, hipStream_t s, const uint8_t **desc);
 void      dfb_launch_place(const DfbCall &b, void *ws, const uint32_t *slots, const uint64_t *block_bits, uint64_t b0, uint32_t nb,
@@ -116,6 +121,11 @@ size_t    dfb_stage_bytes(const DfbCall &b, uint32_t nbmax, uint32_t block);    
 // ---- snappy_batch.hip: the last stage of LZ_SNAPPY — one raw Snappy record per block in its slot, block_bits[lb] = 8 x its bytes
 void      snappy_launch_emit(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_desc, uint32_t block,
                              uint64_t b0, uint32_t nb, hipStream_t s);
+
+// ---- lz4_batch.hip: the last stage of LZ_LZ4 — one LZ4 block record per block in its slot (frame: behind its size word, or the
+// block stored), block_bits[lb] = 8 x the slot's bytes
+void      lz4_launch_emit(const uint32_t *trec, uint32_t *slots, uint64_t *block_bits, const uint8_t *d_desc, uint32_t block,
+                          uint64_t b0, uint32_t nb, bool frame, hipStream_t s);
 
 // ---- inflate_batch.hip: the per-item limit
 #define INFB_MAX_BYTES 0x7FFFFFFFull           // per item, compressed and inflated: positions inside an item are 32-bit

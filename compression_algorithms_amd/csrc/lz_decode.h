@@ -61,6 +61,23 @@ struct BitsLsb {
     __device__ __forceinline__ void skip(uint32_t k) { buf >>= k; have -= k; }
 };
 
+// A reader at a byte boundary of an item of nb bytes at `in` (snappy_batch.hip, lz4_batch.hip), k bytes on (k >= 1; the new
+// position ip_new is inside the item).  Within what the buffer holds it is a shift; within the two register windows the buffer
+// is rebuilt from them (dword indices only grow: WaveWords' rule); farther away the windows are loaded anew there.
+__device__ __forceinline__ void bits_seek_bytes(BitsLsb &br, const uint8_t *in, uint64_t nb, uint32_t ip_new, uint32_t k, uint32_t lane)
+{
+    const uint64_t bits = 8ull * k;
+    if (bits < br.have) { br.skip((uint32_t)bits); return; }
+    const uint64_t t = 32ull * br.widx - br.have + bits;               // the new position, in bits from the reader's first dword
+    const uint64_t d = t >> 5;                                         // >= widx >= w.base
+    if (d - br.w.base < 127u) {
+        const uint32_t bit0 = (uint32_t)(t & 31u), di = (uint32_t)d;
+        const uint32_t lo = br.w.get(di), hi = br.w.get(di + 1u);
+        br.buf = (((uint64_t)hi << 32) | lo) >> bit0;
+        br.have = 64u - bit0; br.widx = di + 2u;
+    } else br.init(in, 8ull * ip_new, 8ull * (nb - ip_new), lane);
+}
+
 // MSB-first reader over u32 words (deflate/huffman.c:16-46 packs MSB first): bit 63 of `buf` is next
 struct BitsMsb {
     WaveWords w;

@@ -617,7 +617,8 @@ __device__ __forceinline__ uint32_t stream_bits(const uint8_t *s, uint64_t nbyte
 // (bgzf.hip).  LZ_BATCH (deflate_batch.hip): mode Z over a batch of independent items — the blocks come from a descriptor table
 // built on the device (d_in, n, d_out, cap_bytes and d_block_bits are not used; nblocks is the caller's bound), and stage C
 // places every record in its own item's buffer instead of scan / concatenate.  LZ_SNAPPY (snappy_batch.hip): LZ_BATCH with raw
-// Snappy records instead of DEFLATE ones — the same descriptor table, tokens and placement, another last stage.
+// Snappy records instead of DEFLATE ones — the same descriptor table, tokens and placement, another last stage.  LZ_LZ4
+// (lz4_batch.hip): the same again with LZ4 block records, an item being one raw block or a frame of them.
 
 // blocks above 64 KiB (lz77 flavour): the HBM-resident finder of lzw.hip, one stream, batches sized by workspace
 static mi_status lz_encode_wide(mi_ctx *ctx, const LzP &P, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap_bytes,
@@ -697,10 +698,10 @@ static mi_status lz_stage_b_solo(mi_ctx *ctx, const LzP &P, uint32_t nb, const L
 mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in, uint64_t n,
                          uint8_t *d_out, uint64_t cap_bytes, uint64_t *d_block_bits, void *stream, const LzCall &c)
 {
-    const bool items = c.form == LZ_BATCH || c.form == LZ_SNAPPY;  // a batch of independent items brings its own buffers
+    const bool items = c.form == LZ_BATCH || c.form == LZ_SNAPPY || c.form == LZ_LZ4;  // a batch of independent items brings its own buffers
     if (!ctx || (!items && (!d_out || !d_block_bits || (n && !d_in)))) return MI_ERR_ARG;
     const bool zform = c.form == LZ_Z || c.form == LZ_BGZF || items;                   // mode Z's tokens: the forms that take parse 1
-    mi_status st = zform ? defz_check(p, c.form == LZ_SNAPPY ? (uint32_t)MI_CONTAINER_RAW : c.container) : lz_check_params(p);
+    mi_status st = zform ? defz_check(p, c.form == LZ_SNAPPY || c.form == LZ_LZ4 ? (uint32_t)MI_CONTAINER_RAW : c.container) : lz_check_params(p);
     if (st) return st;
     if (!items && ((uintptr_t)d_out & 3u) != 0) return MI_ERR_ARG;
     if (c.form == LZ_H && (!p->deflate || p->lbits > 5 || p->wbits > 16)) return MI_ERR_ARG;
@@ -735,7 +736,7 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
     switch (c.form) {
     case LZ_TOKENS: case LZ_H: MI_HIP(ctx, hipMemsetAsync(t.base_bits, 0, 8, s)); break;
     case LZ_Z: case LZ_BGZF:   st = defz_begin(ctx, c.container, d_in, n, d_out, t.base_bits, t.zws, s); break;   // (the base starts at the header's bits)
-    case LZ_BATCH: case LZ_SNAPPY: st = dfb_begin(ctx, bc, P.block, t.zws, s, &d_in); break;                      // (d_in: the descriptor table from here on)
+    case LZ_BATCH: case LZ_SNAPPY: case LZ_LZ4: st = dfb_begin(ctx, bc, P.block, t.zws, s, &d_in); break;                      // (d_in: the descriptor table from here on)
     }
     if (st) return st;
     // behind the last block.  The table of an empty input is its one closing entry (mode Z's epilogue writes it itself, a batch
@@ -746,7 +747,7 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         case LZ_TOKENS: case LZ_H: return MI_OK;
         case LZ_Z:                 return defz_end(ctx, c.container, d_out, d_block_bits, nblocks, n, t.zws, c.d_out_bytes, s);
         case LZ_BGZF:              return bgzf_end(ctx, d_out, d_block_bits, nblocks, c.d_out_bytes, s);
-        case LZ_BATCH: case LZ_SNAPPY: return dfb_end(ctx, bc, P.block, t.zws, s);
+        case LZ_BATCH: case LZ_SNAPPY: case LZ_LZ4: return dfb_end(ctx, bc, P.block, t.zws, s);
         }
         return MI_ERR_ARG;
     };
@@ -774,6 +775,8 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
                           defz_launch_encode(trec, sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, items, sp, dict); };
         auto snappy = [&] { mi_prof_scope ph(ctx, "k_snappy_emit", sp, pbytes);   // raw Snappy records in their slots
                             snappy_launch_emit(trec, sc[k].slot, sc[k].block_bits, d_in, P.block, b0, nb, sp); };
+        auto lz4 = [&] { mi_prof_scope ph(ctx, "k_lz4_emit", sp, pbytes);         // LZ4 block records in their slots
+                         lz4_launch_emit(trec, sc[k].slot, sc[k].block_bits, d_in, P.block, b0, nb, c.container == DFB_LZ4_FRAME, sp); };
         auto frame = [&] { mi_prof_scope pf(ctx, "k_bgzf_frame", sp, pbytes);     // every record a gzip member
                            bgzf_launch_frame(sc[k].slot, sc[k].block_bits, d_in, n, P.block, b0, nb, sp); };
         // every record to its own item (batches reach this stream in order: the item that straddles two of them goes on where the
@@ -795,6 +798,7 @@ mi_status lz_encode_impl(mi_ctx *ctx, const mi_lz_params *p, const uint8_t *d_in
         case LZ_BGZF:   defz(); frame(); concat(); advance(); break;
         case LZ_BATCH:  defz(); place(); break;
         case LZ_SNAPPY: snappy(); place(); break;
+        case LZ_LZ4:    lz4(); place(); break;
         }
     };
     const hipStream_t sf_odd = lz_odd_fallback_stream(ctx, plan, sb);

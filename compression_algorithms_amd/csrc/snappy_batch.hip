@@ -49,23 +49,6 @@ __device__ __forceinline__ uint32_t snappy_preamble(uint64_t nb, Byte byte, uint
     return MI_ERR_CORRUPT;
 }
 
-// the reader k bytes on (k >= 1; the new position is inside the item).  Within what the buffer holds it is a shift; within the
-// two register windows the buffer is rebuilt from them (dword indices only grow: WaveWords' rule); farther away the windows are
-// loaded anew there.
-__device__ __forceinline__ void snappy_seek(BitsLsb &br, const uint8_t *in, uint64_t nb, uint32_t ip_new, uint32_t k, uint32_t lane)
-{
-    const uint64_t bits = 8ull * k;
-    if (bits < br.have) { br.skip((uint32_t)bits); return; }
-    const uint64_t t = 32ull * br.widx - br.have + bits;               // the new position, in bits from the reader's first dword
-    const uint64_t d = t >> 5;                                         // >= widx >= w.base
-    if (d - br.w.base < 127u) {
-        const uint32_t bit0 = (uint32_t)(t & 31u), di = (uint32_t)d;
-        const uint32_t lo = br.w.get(di), hi = br.w.get(di + 1u);
-        br.buf = (((uint64_t)hi << 32) | lo) >> bit0;
-        br.have = 64u - bit0; br.widx = di + 2u;
-    } else br.init(in, 8ull * ip_new, 8ull * (nb - ip_new), lane);
-}
-
 template <uint32_t RING>
 __global__ __launch_bounds__(64)
 void k_snappy_batch(SnapBatch b)
@@ -121,7 +104,7 @@ void k_snappy_batch(SnapBatch b)
                         ring.advance(o);
                     }
                     ip += (uint32_t)len;
-                    if (ip < end) snappy_seek(br, in, nb, ip, (uint32_t)len, lane);
+                    if (ip < end) bits_seek_bytes(br, in, nb, ip, (uint32_t)len, lane);
                 } else {
                     uint32_t len, d;
                     if (kind == 1u) { len = 4u + ((tag >> 2) & 7u); d = ((tag >> 5) << 8) | x; }

@@ -18,7 +18,7 @@ from .context import as_device_bytes, default_context
 def params(flavour="deflate", wbits=None, block=65536, parse=0):
     """parse: 0 the reference's greedy parse; 1 the lazy parse with matches up to 255 bytes, for the standard-DEFLATE writers
     only (compress_z, compress_bgzf, deflate_batch and their host forms; include/mi_codec.h, mode Z) and for
-    snappy_compress_batch, which runs the same pipeline"""
+    snappy_compress_batch and lz4_compress_batch, which run the same pipeline"""
     if flavour == "deflate":
         return _lib.LzParams(15, 5, 20, 1, block, parse)
     if flavour == "lz77":
@@ -1145,3 +1145,147 @@ def snappy_decompress_batch_host(items, ctx=None):
     st = ctx.L.mi_snappy_decode_batch(ctx.h, count, h_in, h_nb, h_out, h_cap, sizes, status, 0)
     _lib.check(st, "mi_snappy_decode_batch")
     return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]
+
+
+# ---- batched LZ4: many independent raw LZ4 blocks (LZ4_compress_default; Parquet LZ4_RAW) or LZ4 frames (the lz4 tool, Arrow IPC) per call
+LZ4_FORMATS = {"block": 0, "frame": 1}                          # MI_LZ4_BLOCK, MI_LZ4_FRAME
+
+
+class Lz4Batch(InflateBatch):
+    """The result of lz4_compress_batch / lz4_decompress_batch: SnappyBatch's shape and meaning"""
+
+    def raise_for_status(self):
+        if self.failed:
+            st = [int(v) for v in self.status.cpu()]
+            i = next(k for k, v in enumerate(st) if v)
+            raise _lib.MiError(st[i], f"lz4 batch: {self.failed} of {len(st)} items failed, the first one item {i}")
+        return self
+
+
+def _lz4_format(format):
+    if format not in LZ4_FORMATS:
+        raise ValueError(f"format must be one of {sorted(LZ4_FORMATS)}, not {format!r}")
+    return LZ4_FORMATS[format]
+
+
+def lz4_batch_bound_bytes(n, p=None, format="frame"):
+    """mi_lz4_batch_bound_bytes: the most an item of n bytes comes to"""
+    p = p or params("deflate")
+    return int(_lib.lib().mi_lz4_batch_bound_bytes(n, C.byref(p), _lz4_format(format)))
+
+
+def _lz4_sizes_dev(ctx, count, d_in, d_nb, fmt):
+    sizes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    st = ctx.L.mi_lz4_batch_size_dev(ctx.h, count, _ptr(d_in), _ptr(d_nb), _ptr(sizes), _ptr(status), None, fmt, ctx.stream_ptr())
+    _lib.check(st, "mi_lz4_batch_size_dev")
+    return sizes[:count], status[:count]
+
+
+def lz4_batch_sizes(items, format="frame", ctx=None):
+    """What every item decodes to -> (sizes int64, status int32) device tensors.  `items` as for lz4_decompress_batch.  The walk of
+    the decoder without its stores, with its verdicts — except that a frame which carries a content size answers from its header
+    alone."""
+    fmt = _lz4_format(format)
+    off, count = _batch_check(items, None)
+    ctx = ctx or default_context()
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    out = _lz4_sizes_dev(ctx, count, d_in, d_nb, fmt)
+    ctx.sync()                                                 # (the inputs in `keep` may go now)
+    return out
+
+
+def _lz4_call(ctx, count, cap, what, call):
+    """one device call `what` into a packed output of the capacities `cap` -> Lz4Batch; call(d_out, d_cap, nbytes, status, failed)"""
+    out, offs, d_out, d_cap = _batch_outputs(ctx, cap, count)
+    nbytes = torch.zeros(max(count, 1), dtype=torch.int64, device=ctx.device)
+    status = torch.zeros(max(count, 1), dtype=torch.int32, device=ctx.device)
+    failed = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+    v0 = ctx.order_violations()
+    _lib.check(call(_ptr(d_out), _ptr(d_cap), _ptr(nbytes), _ptr(status), _ptr(failed)), what)
+    ctx.sync()
+    if ctx.order_violations() != v0:
+        raise _lib.MiError(10, "the encoder that wrote this batch reported a sort out of order")
+    nb, stl = [int(v) for v in nbytes[:count].cpu()], [int(v) for v in status[:count].cpu()]
+    outputs = [out[a:a + (n if s == 0 else 0)] for a, n, s in zip(offs, nb, stl)]
+    return Lz4Batch(outputs, nbytes[:count], status[:count], int(failed.item()) if count else 0)
+
+
+def _caps_list(caps):
+    return [int(v) for v in (caps.cpu().tolist() if torch.is_tensor(caps) else caps)]
+
+
+def lz4_decompress_batch(items, format="frame", caps=None, ctx=None):
+    """Decode many independent LZ4 buffers in one launch -> Lz4Batch.
+
+    items: a list of bytes or uint8 tensors, or a pair (buffer, offsets) for a packed buffer with count + 1 offsets (item i is
+    buffer[offsets[i]:offsets[i + 1]]: no alignment needed).  format: "frame" (the lz4 tool's, Arrow IPC's) or "block" (a raw
+    block: Parquet LZ4_RAW).  caps: the output capacity of every item (list or tensor); None runs the size walk first and
+    allocates one packed output.  An item larger than its capacity comes back MI_ERR_CAPACITY with out_bytes = the size it needs
+    and nothing written at or past the capacity; a malformed one MI_ERR_CORRUPT; one bad item does not spoil the rest.  Block and
+    content checksums of a frame are skipped over, not verified."""
+    fmt = _lz4_format(format)
+    off, count = _batch_check(items, caps)
+    ctx = ctx or default_context()
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    cap = _caps_list(_lz4_sizes_dev(ctx, count, d_in, d_nb, fmt)[0] if caps is None else caps)
+    return _lz4_call(ctx, count, cap, "mi_lz4_decode_batch_dev", lambda *o: ctx.L.mi_lz4_decode_batch_dev(
+        ctx.h, count, _ptr(d_in), _ptr(d_nb), *o, fmt, 0, ctx.stream_ptr()))
+
+
+def lz4_compress_batch(items, p=None, format="frame", caps=None, ctx=None, max_blocks=None):
+    """Compress many independent buffers in one call, each to an LZ4 frame or a raw LZ4 block that stock LZ4 reads -> Lz4Batch.
+
+    items: as for lz4_decompress_batch.  p: params("deflate", block=..., parse=0 or 1) — the batched deflate's finder, parse and
+    blocks.  format "frame": any size; one frame block per pipeline block, independent blocks, no checksums, no content size.
+    format "block": an item is ONE block, so an item above p.block bytes comes back MI_ERR_ARG (alone).  caps: the output capacity
+    of every item; None gives each item its bound in one packed output.  An item that does not fit its capacity comes back
+    MI_ERR_CAPACITY with out_bytes = the size it needs.  max_blocks: the launch bound (None: from the sizes, which are known here;
+    a raw-block item above the block size is refused and has no blocks)."""
+    fmt = _lz4_format(format)
+    off, count = _batch_check(items, caps)
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    keep, d_in, d_nb = _batch_inputs(ctx, items, off, count)
+    sizes = [int(v) for v in d_nb.cpu()] if count else []
+    cap = [lz4_batch_bound_bytes(n, p, format) for n in sizes] if caps is None else _caps_list(caps)
+    if max_blocks is None:
+        max_blocks = sum((n + p.block - 1) // p.block for n in sizes if n <= 0x7FFFFFFF and (fmt or n <= p.block))
+    return _lz4_call(ctx, count, cap, "mi_lz4_encode_batch_dev", lambda *o: ctx.L.mi_lz4_encode_batch_dev(
+        ctx.h, C.byref(p), fmt, count, _ptr(d_in), _ptr(d_nb), max_blocks, *o, ctx.stream_ptr()))
+
+
+def _lz4_host(count, caps, call):
+    """one host-buffer call into outputs of the capacities `caps` -> (list of bytes, None where the item failed; list of status codes)"""
+    outs = [np.zeros(max(v, 1), dtype=np.uint8) for v in caps]
+    h_out = (C.c_void_p * max(count, 1))(*[o.ctypes.data for o in outs])
+    sizes, status = call(h_out, (C.c_uint64 * max(count, 1))(*caps))
+    return [outs[i][: int(sizes[i])].tobytes() if status[i] == 0 else None for i in range(count)], [int(status[i]) for i in range(count)]
+
+
+def lz4_compress_batch_host(items, p=None, format="frame", ctx=None):
+    """the host-buffer entry point (mi_lz4_encode_batch): a list of bytes -> (list of bytes, None where the item failed; list of
+    status codes)"""
+    fmt = _lz4_format(format)
+    ctx = ctx or default_context()
+    p = p or params("deflate")
+    arrs, h_in, h_nb, sizes, status = _host_arrays([bytes(x) for x in items])
+
+    def call(h_out, h_cap):
+        _lib.check(ctx.L.mi_lz4_encode_batch(ctx.h, C.byref(p), fmt, len(arrs), h_in, h_nb, h_out, h_cap, sizes, status), "mi_lz4_encode_batch")
+        return sizes, status
+    return _lz4_host(len(arrs), [lz4_batch_bound_bytes(a.size, p, format) for a in arrs], call)
+
+
+def lz4_decompress_batch_host(items, format="frame", ctx=None):
+    """the host-buffer entry point (mi_lz4_decode_batch, called once for the sizes and once to decode, so the inputs travel to the
+    device twice: a convenience path): a list of bytes -> (list of bytes, None where the item failed; list of status codes)"""
+    fmt = _lz4_format(format)
+    ctx = ctx or default_context()
+    arrs, h_in, h_nb, sizes, status = _host_arrays([bytes(x) for x in items])
+
+    def call(h_out, h_cap):
+        _lib.check(ctx.L.mi_lz4_decode_batch(ctx.h, len(arrs), h_in, h_nb, h_out, h_cap, sizes, status, fmt, 0), "mi_lz4_decode_batch")
+        return sizes, status
+    call(None, None)
+    return _lz4_host(len(arrs), [int(sizes[i]) for i in range(len(arrs))], call)

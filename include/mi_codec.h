@@ -805,6 +805,93 @@ mi_status mi_snappy_decode_batch(mi_ctx *ctx, uint64_t count, const void *const 
                                  uint32_t flags);
 
 /* ------------------------------------------------------------------------------------
+ * Batched LZ4: many independent LZ4 buffers encoded or decoded in one call, in one of two
+ * formats chosen per call:
+ *   MI_LZ4_BLOCK  a RAW block (lz4_Block_format.md; what LZ4_compress_default writes and
+ *                 LZ4_decompress_safe reads): Parquet LZ4_RAW, ORC, zarr / blosc, ClickHouse, RocksDB.
+ *                 Sequences of token (literal-length nibble high, match-length nibble low), a chain
+ *                 of 255-valued bytes behind a nibble of 15, the literals, a 2-byte little-endian
+ *                 offset, the match-length chain (match length = nibble + chain + 4); the last
+ *                 sequence is literals only and ends exactly at the item's end.  A block does not
+ *                 name its size.
+ *   MI_LZ4_FRAME  a frame (lz4_Frame_format.md; the `lz4` tool, Arrow IPC / Feather buffers):
+ *                 magic 04 22 4D 18, FLG, BD, optional content size, HC, then blocks behind 4-byte
+ *                 size words (top bit: stored) up to the EndMark 00 00 00 00.
+ * OUT OF SCOPE: dictionaries, skippable and concatenated frames, the legacy frame, Hadoop's LZ4
+ * wrapper, LZ4-HC parsing, and XXH32 beyond the header's HC byte — the encoder writes no block or
+ * content checksum, and the decoder SKIPS OVER both without verifying them (`flags` must be 0 and
+ * is reserved for a later verify).
+ * Arrays, addresses, verdicts, *d_failed, count == 0 and asynchrony: exactly as for the batched
+ * Snappy above.
+ *
+ * mi_lz4_decode_batch_dev — one wave per item.  Loads stay inside the aligned dwords that cover
+ * the item; every bound is checked before an element stores; no byte at or past d_out_cap[i] is
+ * stored.  Neither format has to name its size, so a capacity works as in mi_inflate_batch_dev:
+ * past it the walk goes on without stores.
+ *   MI_OK            d_out_bytes[i] = the bytes written.  The single byte 00 is a block of 0 bytes.
+ *   MI_ERR_CAPACITY  well-formed to its end, but larger than d_out_cap[i]: d_out_bytes[i] = the
+ *                    size it needs; bytes below the capacity unspecified.
+ *   MI_ERR_CORRUPT   d_out_bytes[i] = 0, bytes below the capacity unspecified: an item of 0 bytes;
+ *                    offset 0 or an offset above the bytes written (with B.Indep = 1: above the bytes
+ *                    written by its block); input that ends inside a sequence, or a block that does
+ *                    not end with a literals-only sequence.  Frame: a wrong magic, version, reserved
+ *                    bit, BD, or HC (which IS checked); block data or block output above the BD
+ *                    maximum; a missing EndMark or checksum field; a content size that is not the
+ *                    decoded length; bytes behind the frame.
+ *                    The decoder does NOT enforce the encoder-side end rules (last 5 bytes literal,
+ *                    last match starting >= 12 bytes before the end): the specification leaves
+ *                    those to encoders.
+ *   MI_ERR_ARG       d_out_bytes[i] = 0: a NULL pointer with a non-zero size or capacity; a size,
+ *                    capacity, content size or decoded length above 2^31 - 1; well-formed but
+ *                    unsupported — a frame with a DictID, a skippable-frame or the legacy magic.
+ * mi_lz4_batch_size_dev — one thread per item, the same walk without stores and the same
+ * verdicts, EXCEPT that a frame which carries a content size answers from its header alone (its
+ * body is not looked at, as for mi_snappy_batch_size_dev).
+ *
+ * mi_lz4_encode_batch_dev — the batched deflate's pipeline (finder, parse 0 or 1, blocks) with LZ4
+ * sequences as its last stage.  p and max_blocks: exactly as for mi_snappy_encode_batch_dev.  The
+ * bytes are deterministic.  Per block of n bytes, over the token sequence: a literal joins the
+ * pending run; a match (L, d) at position p joins it too when p + 12 > n, or when
+ * L = min(L, n - 5 - p) leaves L < 4 (the format's end rules, which stock decoders enforce; the
+ * bytes a shortened match no longer covers begin the next run); any other match flushes the run
+ * and itself as one sequence; the run pending at the block's end is the closing literals-only
+ * sequence, so a block below 13 bytes is all literals.
+ *   MI_LZ4_BLOCK: an item is ONE block — no header, no trailer, an empty item the byte 00.  An item
+ *   with in_bytes > p->block is MI_ERR_ARG for that item alone (it takes none of max_blocks).
+ *   Items of several pipeline blocks are not written: a block's closing run would have to merge
+ *   into the next block's first sequence, a dependency along the item the pipeline has no place for.
+ *   MI_LZ4_FRAME: an item of any size up to 2^31 - 1 is 04 22 4D 18 60 40 82 (version 1,
+ *   independent blocks, no checksums, no content size, 64 KiB maximum), one frame block per
+ *   pipeline block — the size word and the record, or, where the record would not be shorter than
+ *   the block, n | 0x80000000 and the block's bytes — and 00 00 00 00.  An empty item is those 11 bytes.
+ *   MI_OK / MI_ERR_CAPACITY (d_out_bytes[i] = the exact size needed, nothing written at or past the
+ *   capacity) / MI_ERR_ARG (also: blocks beyond max_blocks) as for mi_deflate_batch_dev.
+ * mi_lz4_batch_bound_bytes(n, p, format): block n + n / 255 + 16 (LZ4_compressBound; a sequence
+ * is at most r / 255 bytes longer than the r literals and the match it covers, the closing one
+ * 2 + r / 255); frame 11 + n + 4 ceil(n / block).
+ * The host forms: as mi_snappy_encode_batch / mi_snappy_decode_batch.
+ * ------------------------------------------------------------------------------------ */
+#define MI_LZ4_BLOCK 0u
+#define MI_LZ4_FRAME 1u
+uint64_t  mi_lz4_batch_bound_bytes(uint64_t n_item, const mi_lz_params *p, uint32_t format);
+uint64_t  mi_lz4_batch_max_blocks(uint64_t total_in_bytes, uint64_t count, const mi_lz_params *p);   /* total / block + count */
+mi_status mi_lz4_encode_batch_dev(mi_ctx *ctx, const mi_lz_params *p, uint32_t format, uint64_t count,
+                                  const void *const *d_in, const uint64_t *d_in_bytes, uint64_t max_blocks,
+                                  void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                                  uint32_t *d_status, uint32_t *d_failed, void *stream);
+mi_status mi_lz4_decode_batch_dev(mi_ctx *ctx, uint64_t count, const void *const *d_in, const uint64_t *d_in_bytes,
+                                  void *const *d_out, const uint64_t *d_out_cap, uint64_t *d_out_bytes,
+                                  uint32_t *d_status, uint32_t *d_failed, uint32_t format, uint32_t flags, void *stream);
+mi_status mi_lz4_batch_size_dev(mi_ctx *ctx, uint64_t count, const void *const *d_in, const uint64_t *d_in_bytes,
+                                uint64_t *d_out_bytes, uint32_t *d_status, uint32_t *d_failed, uint32_t format, void *stream);
+mi_status mi_lz4_encode_batch(mi_ctx *ctx, const mi_lz_params *p, uint32_t format, uint64_t count,
+                              const void *const *h_in, const uint64_t *h_in_bytes,
+                              void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status);
+mi_status mi_lz4_decode_batch(mi_ctx *ctx, uint64_t count, const void *const *h_in, const uint64_t *h_in_bytes,
+                              void *const *h_out, const uint64_t *h_out_cap, uint64_t *h_out_bytes, uint32_t *h_status,
+                              uint32_t format, uint32_t flags);
+
+/* ------------------------------------------------------------------------------------
  * FSE / tANS, block-parallel (fse/src/main.zig — an unfinished sketch; the stream format is
  * defined by this build).  Record layout in include/mi_fse.h.
  * ------------------------------------------------------------------------------------ */
